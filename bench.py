@@ -1,14 +1,26 @@
 """bench.py -- BASELINE.json metric: fwd+bwd iters/s and HBM GB/s at 2M Gaussians, 1920x1080.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up the view, runs W warm-up and K timed binning steps (`step` below), writes the
+  last step's outputs when --dump-outputs is given and prints the result line: the headline fields,
+  the configuration, `ms_per_step` (one timed step) and the `binning_step` rates.  Everything else
+  below -- per-kernel durations and the roofline, the skewed view, distCUDA2, the config scales, the
+  masked Adam, the exchange legs, dp_step and the CPU baselines -- takes runs of its own and is
+  measured only with --full.
+  --dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned as
+  float64 DIR/<name>.npy: point_offsets (the scan), sorted_keys, sorted_values, tile_ranges.  An
+  array over DUMP_CAP elements is written as a fixed sample (seeded, increasing positions).  The
+  scene is seeded, so the same arguments give the same inputs in every run.
   N > 1 without a torch.distributed environment: this process starts
   `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a child (before touching
   any GPU), relays rank 0's JSON line and exits with the child's status.  Under the driver's
   own torch.distributed.run launch the ranks are already there.  --backend gloo runs the
-  multi-rank plumbing on CPU (the exchange leg only; tests/test_bench.py).
+  multi-rank plumbing on CPU (with --full: the exchange leg only; tests/test_bench.py).
 
 The headline metric needs the rasterizer forward + backward, whose kernels were refused
-("Decisions in force"), so `value` is null -- never estimated.  What the repo builds
+("Decisions in force"), so it is never estimated: `headline_value` is null.  `value` is
+what the timed steps measure, and `metric` says so: binning steps per second over all ranks
+(world / ms_per_step; null only where no step runs, --backend gloo).  What the repo builds
 on this path is measured for real, at the configuration the metric is quoted on (config 3:
 2M Gaussians, one 1920x1080 view per rank, synthetic D2 scene resident in HBM):
 
@@ -79,6 +91,7 @@ ROCPROF_NAME = {"radix_scatter_u64": "radix_scatter_kernel", "segment_sort": "se
                 "scan_reduce": "scan_reduce_kernel"}
 # the binning sort's kernels (every launch of hidegs_sort_tile_pairs)
 SORT_KERNELS = ("radix_hist_u64", "radix_digit_scan", "radix_scatter_u64", "segment_sort", "big_segments", "piece_sort")
+DUMP_CAP = 2_000_000  # --dump-outputs: elements per array (three sampled float64 arrays of 16 MB + the tile ranges)
 
 
 def sources_sha256() -> str:
@@ -110,6 +123,20 @@ def traffic_entry(dom: str, K: int, T: int, table: dict):
     if same:
         return max(same, key=lambda kv: kv[1].get("launches", 0))
     return None, None
+
+
+def dump_outputs(dirname: str, arrays: dict, np, torch) -> None:
+    """--dump-outputs: each integer tensor's unsigned bit patterns as float64 `dirname/<name>.npy` (exact
+    below 2^53: keys are 45-bit here).  More than DUMP_CAP elements: the flattened tensor at DUMP_CAP
+    increasing positions drawn once from a fixed seed, the same in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
 
 
 def free_port() -> int:
@@ -190,6 +217,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the timed binning step: per-kernel durations and the "
+                         "roofline, the skewed view, distCUDA2, the config scales, masked Adam, the exchange "
+                         "legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float64 DIR/<name>.npy (rank 0)")
     ap.add_argument("--knn-steps", type=int, default=5)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo: CPU ranks, the exchange leg only (plumbing tests)")
@@ -290,8 +323,11 @@ def main() -> None:
         return max_over_ranks(dev_ms), max_over_ranks(wall)
 
     line = {
-        "metric": "fwd+bwd iters/sec & HBM GB/s at 2M Gaussians, 1920x1080",
+        "metric": "binning-stage iters/sec at 2M Gaussians, 1920x1080 (scan + tile sort + ranges, the built part of "
+                  "the fwd+bwd iteration; the rasterizer fwd/bwd is not built: headline_metric, status)",
         "value": None,
+        "headline_metric": "fwd+bwd iters/sec & HBM GB/s at 2M Gaussians, 1920x1080",
+        "headline_value": None,
         "unit": "iters/s",
         "n_gpus": world,
         "steps": args.steps,
@@ -308,7 +344,7 @@ def main() -> None:
                    "n_gaussians": N, "width": W_PX, "height": H_PX, "parallelism": f"view-dp{world}",
                    "backend": "rccl" if gpu else "gloo"},
         "status": "headline UNMEASURED: the rasterizer forward/backward kernels were refused "
-                  "(DESIGN.md, 'Decisions in force'); value stays null",
+                  "(DESIGN.md, 'Decisions in force'); headline_value stays null, value is the binning stage's rate",
         "roofline": None,
         "cpu_baseline": None,
         "fail_fast": {"process_group_timeout_s": args.pg_timeout, "exchange_host_wait_timeout_s": args.pg_timeout,
@@ -322,9 +358,9 @@ def main() -> None:
     ctx = {}
     if gpu:
         _gpu_legs(args, line, ctx, world, rank, dev, cam, scene, timed, np, torch)
-    if not args.no_exchange:
+    if args.full and not args.no_exchange:
         _exchange_legs(args, line, ctx, world, rank, dev, N, timed, gpu, torch, GradArena, ViewDPExchange)
-    if gpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and gpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
         _cpu_baselines(line, ctx, N, cam, np)
 
     dist.destroy_process_group()
@@ -354,15 +390,31 @@ def _gpu_legs(args, line, ctx, world, rank, dev, cam, scene, timed, np, torch):
 
     def make_step(w):
         off = torch.empty_like(w.tiles_touched)
+        held = []  # the last step's (sorted keys, sorted values, tile ranges), for --dump-outputs
 
         def step():
+            held.clear()  # before the sort, as when nothing was kept: the allocator hands out the same blocks again
             primitives.inclusive_scan_u32(w.tiles_touched, out=off)
-            primitives.sort_tile_pairs(w.keys, w.values, w.num_tiles)  # SortPairs + identifyTileRanges
+            held.append(primitives.sort_tile_pairs(w.keys, w.values, w.num_tiles))  # SortPairs + identifyTileRanges
+        step.outputs = lambda: (off, *held[0])
         return step
 
     step = make_step(wl)
     ms_step, wall_ms_step = timed(step, args.steps, args.warmup)
     qerr = primitives.queue_error()
+    if args.dump_outputs and rank == 0:
+        offs, keys_sorted, values_sorted, tile_ranges = step.outputs()
+        dump_outputs(args.dump_outputs, {"point_offsets": offs, "sorted_keys": keys_sorted,
+                                         "sorted_values": values_sorted, "tile_ranges": tile_ranges}, np, torch)
+    line["ms_per_step"] = line["ms_per_step_binning"] = round(ms_step, 4)
+    line["value"] = world / (ms_step * 1e-3)
+    line["binning_step"] = {"ms_per_step": round(ms_step, 4), "wall_ms_per_step": round(wall_ms_step, 4),
+                            "timed_region": "inclusive scan of tiles_touched + hidegs_sort_tile_pairs (sort + "
+                                            "tile ranges); no key emission, no rasterizer",
+                            "pairs_per_s_all_ranks": K * world / (ms_step * 1e-3),
+                            "binning_steps_per_s_all_ranks": world / (ms_step * 1e-3), "queue_error": qerr}
+    if not args.full:
+        return
 
     # per-kernel durations of the same step, live, with per-launch HIP events on the launch stream
     kt_steps = max(10, min(args.steps, 50))
@@ -402,12 +454,7 @@ def _gpu_legs(args, line, ctx, world, rank, dev, cam, scene, timed, np, torch):
         with open(TRAFFIC_META) as f:
             meta = json.load(f)
     sort_us = sum(kern[k]["us_per_step"] for k in kern if k in SORT_KERNELS)
-    line["binning_step"] = {"ms_per_step": round(ms_step, 4), "wall_ms_per_step": round(wall_ms_step, 4),
-                            "timed_region": "inclusive scan of tiles_touched + hidegs_sort_tile_pairs (sort + "
-                                            "tile ranges); no key emission, no rasterizer",
-                            "pairs_per_s_all_ranks": K * world / (ms_step * 1e-3),
-                            "binning_steps_per_s_all_ranks": world / (ms_step * 1e-3),
-                            "sort_us": round(sort_us, 2), "queue_error": qerr, "kernels": kern}
+    line["binning_step"].update({"sort_us": round(sort_us, 2), "kernels": kern})
     line["roofline"] = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                         "traffic": None if traffic is None else round(traffic),
@@ -418,7 +465,6 @@ def _gpu_legs(args, line, ctx, world, rank, dev, cam, scene, timed, np, torch):
                         "traffic_profile_same_source": (meta.get("sources_sha256") == sources_sha256()
                                                         if meta.get("sources_sha256") else None),
                         "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": dom_us}
-    line["ms_per_step_binning"] = round(ms_step, 4)
 
     # ---- the same step on a skewed view (hot tiles through the partition queue) ----------------
     if not args.no_skewed and world == 1:  # single-GPU sub-metric (N > 1 ranks skip its CPU-side scene)

@@ -20,7 +20,7 @@ def test_bench_launches_its_own_ranks_gloo(gpus):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MASTER_ADDR"] = "127.0.0.1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo",
-                          "--n-gaussians", "20000", "--steps", "2", "--warmup", "1"],
+                          "--n-gaussians", "20000", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -35,7 +35,78 @@ def test_bench_launches_its_own_ranks_gloo(gpus):
     bx = rec["exchange_bf16"]
     assert bx["wire_bytes_per_rank"] * 2 == bx["grad_bytes_per_rank"] and bx["collectives_per_step"] > 0
     assert bx["replicas_bit_identical"] is True
-    assert rec["value"] is None  # the headline stays unmeasured
+    assert rec["value"] is None and rec["headline_value"] is None  # gloo: no timed step; the headline stays unmeasured
+
+
+def _run_bench(*argv):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["MASTER_ADDR"] = "127.0.0.1"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True,
+                         timeout=300, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+HEADLINE_FIELDS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY = ("exchange", "exchange_bf16", "exchange_and_step", "dp_step", "distCUDA2", "masked_adam",
+             "binning_skewed", "config2_scale", "config5_scale")
+
+
+def test_plain_run_measures_nothing_beside_its_step_gloo():
+    """Without --full the exchange legs (all a gloo run has) are not run; the line keeps its headline fields."""
+    rec = _run_bench("--gpus", "1", "--backend", "gloo", "--n-gaussians", "20000", "--steps", "2", "--warmup", "1")
+    assert all(k in rec for k in HEADLINE_FIELDS)
+    assert not [k for k in FULL_ONLY if k in rec] and rec["cpu_baseline"] is None and rec["roofline"] is None
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_its_outputs(tmp_path):
+    """A plain one-GPU run: `steps` timed steps, ms_per_step in the line, nothing that --full adds, and
+    --dump-outputs writes the last step's scan, sorted pairs and tile ranges, which are checked against
+    the pairs' definition: keys non-decreasing and each tile's range holding exactly its keys."""
+    import numpy as np
+    rec = _run_bench("--gpus", "1", "--n-gaussians", "20000", "--steps", "3", "--warmup", "1",
+                     "--dump-outputs", str(tmp_path / "a"))
+    assert all(k in rec for k in HEADLINE_FIELDS) and rec["steps"] == 3 and rec["warmup"] == 1
+    assert rec["ms_per_step"] > 0 and rec["ms_per_step"] == rec["binning_step"]["ms_per_step"]
+    assert rec["value"] == rec["binning_step"]["binning_steps_per_s_all_ranks"] and 0 < rec["value"] < float("inf")
+    assert rec["headline_value"] is None and rec["unit"] == "iters/s" and rec["higher_is_better"] is True
+    assert rec["binning_step"]["queue_error"] == 0 and "kernels" not in rec["binning_step"]
+    assert not [k for k in FULL_ONLY if k in rec] and rec["cpu_baseline"] is None and rec["roofline"] is None
+    out = {n: np.load(tmp_path / "a" / f"{n}.npy")
+           for n in ("point_offsets", "sorted_keys", "sorted_values", "tile_ranges")}
+    assert all(a.dtype == np.float64 for a in out.values())
+    K, T = rec["config"]["pairs_K"], rec["config"]["tiles"]
+    keys = out["sorted_keys"].astype(np.uint64)
+    assert keys.shape == (K,) and out["sorted_values"].shape == (K,) and out["tile_ranges"].shape == (T, 2)
+    assert out["point_offsets"].shape == (20000,) and out["point_offsets"][-1] == K
+    assert np.all(np.diff(out["point_offsets"]) >= 0) and np.all(keys[1:] >= keys[:-1])
+    assert out["sorted_values"].min() >= 0 and out["sorted_values"].max() < 20000
+    tiles = (keys >> np.uint64(32)).astype(np.int64)
+    counts = np.bincount(tiles, minlength=T)
+    ends = np.cumsum(counts)
+    filled = counts > 0
+    assert np.array_equal(out["tile_ranges"][filled, 1], ends[filled])
+    assert np.array_equal(out["tile_ranges"][filled, 0], (ends - counts)[filled])
+    assert np.all(out["tile_ranges"][~filled] == 0)
+
+
+def test_dump_outputs_samples_large_arrays_at_fixed_positions(tmp_path):
+    import numpy as np
+    import torch
+    big = torch.arange(bench.DUMP_CAP + 12345, dtype=torch.int32)
+    small = torch.tensor([[0, 3], [3, 7]], dtype=torch.int32)
+    keys = torch.tensor([(5 << 32) | 0xFFFFFFFF, 1 << 44], dtype=torch.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "keys": keys}, np, torch)
+    a = np.load(tmp_path / "a" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (bench.DUMP_CAP,) and np.all(np.diff(a) > 0)  # values = positions
+    assert np.array_equal(a, np.load(tmp_path / "b" / "big.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), [[0.0, 3.0], [3.0, 7.0]])
+    assert np.array_equal(np.load(tmp_path / "a" / "keys.npy"), [float((5 << 32) | 0xFFFFFFFF), float(1 << 44)])
+    assert 4 * bench.DUMP_CAP * 8 <= 64 * 2 ** 20  # four arrays at the cap stay within 64 MB
 
 
 def test_cpu_share_reports_its_evidence():

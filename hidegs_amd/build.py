@@ -13,6 +13,7 @@ that the product build cannot reach (e.g. a tiny partition-queue job capacity).
 from __future__ import annotations
 
 import concurrent.futures as cf
+import glob
 import hashlib
 import os
 import shutil
@@ -26,7 +27,8 @@ OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhidegs.so")
 VARIANT_DIR = os.path.join(HERE, "variants")
 SOURCES = ["abi.cpp", "timing.cpp", "primitives.hip", "knn.hip", "adam.hip", "wire.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "block_scan.h"), os.path.join(INCLUDE, "hidegs.h")]
+# every header: a change to any of them rebuilds every object
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "hidegs.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf, so the
 # oracle (oracle/knn_ref.c) can reproduce each rounding step bit for bit.
@@ -118,25 +120,26 @@ def variant_path(tag: str) -> str:
     return os.path.join(VARIANT_DIR, f"libhidegs_{tag}.so")
 
 
+def _compile_all(sources, objdir: str, defines, verbose: bool) -> list:
+    os.makedirs(objdir, exist_ok=True)
+    with cf.ThreadPoolExecutor(max_workers=8) as ex:
+        return list(ex.map(lambda s: _compile(os.path.join(CSRC, s), objdir, defines, verbose), sources))
+
+
+def build_variant(tag: str, defines, changed=SOURCES, verbose: bool = False) -> str:
+    """hidegs_amd/variants/libhidegs_<tag>.so: the library with `defines` on the `changed` sources; the
+    other objects are the product build's (compiled here if stale)."""
+    objs = dict(zip(changed, _compile_all(changed, os.path.join(VARIANT_DIR, "obj_" + tag), defines, verbose)))
+    rest = [s for s in SOURCES if s not in objs]
+    objs.update(zip(rest, _compile_all(rest, OBJDIR, [], verbose)))
+    return _link([objs[s] for s in SOURCES], variant_path(tag), verbose)
+
+
 def build(verbose: bool = False, variants: bool = True) -> str:
-    os.makedirs(OBJDIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    jobs = [(s, OBJDIR, []) for s in srcs]
+    _link(_compile_all(SOURCES, OBJDIR, [], verbose), LIB, verbose)
     if variants:
-        for tag, (defs, changed) in VARIANTS.items():
-            vdir = os.path.join(VARIANT_DIR, "obj_" + tag)
-            os.makedirs(vdir, exist_ok=True)
-            jobs += [(os.path.join(CSRC, s), vdir, defs) for s in changed]
-    with cf.ThreadPoolExecutor(max_workers=min(len(jobs), 8)) as ex:
-        objs = list(ex.map(lambda j: _compile(j[0], j[1], j[2], verbose), jobs))
-    base = objs[:len(srcs)]
-    _link(base, LIB, verbose)
-    if variants:
-        k = len(srcs)
-        for tag, (defs, changed) in VARIANTS.items():
-            own = dict(zip(changed, objs[k:k + len(changed)]))
-            k += len(changed)
-            _link([own.get(s, o) for s, o in zip(SOURCES, base)], variant_path(tag), verbose)
+        with cf.ThreadPoolExecutor(max_workers=len(VARIANTS)) as ex:  # the product objects are fresh: no two compile one file
+            list(ex.map(lambda tv: build_variant(tv[0], *tv[1], verbose=verbose), VARIANTS.items()))
         build_abi_client(verbose)
     return LIB
 

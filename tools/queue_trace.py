@@ -2,7 +2,7 @@
 
 Needs a library built with -DHIDEGS_QUEUE_TRACE:
     python tools/build_variant.py qtrace -DHIDEGS_QUEUE_TRACE=1
-    HIDEGS_LIB=variants/libhidegs_qtrace.so python tools/queue_trace.py [hot_pairs ...]
+    HIDEGS_LIB=hidegs_amd/variants/libhidegs_qtrace.so python tools/queue_trace.py [hot_pairs ...]
 Times are wall_clock64 ticks (100 MHz) relative to the first claim, in microseconds."""
 import ctypes as C
 import os

@@ -4,7 +4,7 @@ usage: python tools/skew_time.py [FRACTION:RADIUS ...]   (default: none, 0.05:0.
 Each line: tile-size profile of the view, whole hidegs_sort_tile_pairs (HIP events, median of 5 x 5
 calls) and segment_sort / big_segments per call (library events), and a check of the result against
 torch's stable sort of the same keys (values compared: equal keys keep input order).
-Run against a variant with HIDEGS_LIB=variants/libhidegs_TAG.so (tools/build_variant.py).
+Run against a variant with HIDEGS_LIB=hidegs_amd/variants/libhidegs_TAG.so (tools/build_variant.py).
 """
 import os
 import statistics

@@ -482,8 +482,11 @@ class ViewDPExchange:
         updates its rows -- so the update of bucket b runs while buckets b+1... are still on the
         wire, and only the last bucket's update is exposed.  The field order ends with the narrow
         fields, so that last bucket is small.  The compacted exchange (few union rows) and a
-        one-rank group step once after the exchange.  The result is bit-identical to `exchange`
-        then `optimizer.step(union)`: the update is row-local and every row is updated once.
+        one-rank group step once after the exchange.  Given the same summed gradients the result is
+        bit-identical to `exchange` then `optimizer.step(union)`: the update is row-local and every
+        row is updated once.  (The bf16 transport defines each element's sum; an fp32 all-reduce may
+        add the ranks in an order that depends on an element's place in its bucket, and the two
+        paths cut the buckets differently, so above two ranks their sums can differ in the last bit.)
         """
         if not isinstance(arena, GradArena):
             raise TypeError("exchange_and_step works on a GradArena")

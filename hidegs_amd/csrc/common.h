@@ -53,6 +53,11 @@ int take_async_error(const char* what, hipStream_t stream);
 // `stream`'s word's bits and the graph word's, taken (exchanged with 0); 0 when none are pending.
 uint32_t take_async_bits(hipStream_t stream);
 
+// The stable u64-key radix sort over key bits [b, e) (primitives.hip), as distCUDA2 (knn.hip) calls it.
+size_t sort_u64_scratch(long long n);
+int sort_pairs_u64(void* scratch, size_t bytes, const uint64_t* ki, uint64_t* ko, const uint32_t* vi, uint32_t* vo,
+                   long long n, int b, int e, hipStream_t s);
+
 // 256-byte aligned carving of one caller-provided scratch buffer.
 constexpr size_t kAlign = 256;
 inline size_t align_up(size_t n) { return (n + kAlign - 1) & ~(kAlign - 1); }
@@ -80,7 +85,6 @@ __device__ __forceinline__ int lane_id() { return __lane_id(); }
 // XCD a contiguous range of indices.
 __device__ __forceinline__ int xcd_swizzle(int b, int nb)
 {
-    // consecutive leaf groups land on one XCD (blocks b, b+8, ... share an XCD's L2)
     const int per = nb / 8, rem = nb % 8, x = b % 8, k = b / 8;
     return (x < rem) ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
 }

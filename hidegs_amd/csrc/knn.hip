@@ -34,17 +34,11 @@
 #include <float.h>
 
 #include <algorithm>
-#include <vector>
-#include <cstdio>
-#include <cstdlib>
 
 #include "common.h"
+#include "knn_stats.h"
 
 namespace hidegs {
-
-size_t sort_u64_scratch(long long n);
-int sort_pairs_u64(void* scratch, size_t bytes, const uint64_t* ki, uint64_t* ko, const uint32_t* vi, uint32_t* vo,
-                   long long n, int b, int e, hipStream_t s);
 
 namespace {
 
@@ -53,15 +47,10 @@ constexpr int kWaves = kBlock / kWave;  // 4 waves = 4 leaves per workgroup
 constexpr int kLeaf = 64;               // points per leaf
 constexpr int kFan = 64;                // leaves per super-box
 constexpr int kSub = 4;                 // sub-boxes per leaf (16 points each): the fine filter
-#ifndef HIDEGS_KNN_MORTON_BITS
-#define HIDEGS_KNN_MORTON_BITS 16
-#endif
-constexpr int kMortonBits = HIDEGS_KNN_MORTON_BITS;  // per axis (the sort runs over 3x these bits)
-#ifndef HIDEGS_KNN_SORT_BEGIN
-#define HIDEGS_KNN_SORT_BEGIN 0  // low Morton bits left out of the sort (the order changes speed only)
-#endif
-constexpr int kSortBegin = HIDEGS_KNN_SORT_BEGIN;
-static_assert(kSortBegin >= 0 && kSortBegin < 3 * kMortonBits, "HIDEGS_KNN_SORT_BEGIN: inside the code");
+// Per axis; the sort runs over all 3x these bits.  10 bits sort in 4 passes instead of 6 but the coarser
+// order costs the search as much; a sort over the high bits only loses the dense region of a cloud whose
+// outliers inflate the bounding box.
+constexpr int kMortonBits = 16;
 constexpr int kBoundBlocks = 1024;
 constexpr float kHardFactor = 8.0f;     // 3rd-best above 8x the wave mean -> phase 2
 
@@ -99,15 +88,12 @@ __device__ __forceinline__ float box_box_lb(const Box& b, float4 qlo, float4 qhi
 // Every value here is a non-negative float (a sum of squares, FLT_MAX or +inf), whose bit
 // patterns order like unsigned integers: the min/max network runs on the bits, which spares the
 // NaN-quieting canonicalisation that fminf/fmaxf of loop-carried values costs on gfx950.
-// No NaN test is needed (HIDEGS_KNN_NAN_CHECK=1 restores it for A/B): the three best only decrease
+// No NaN test is needed (dropping it: knn_leaf frustum 959 -> 896 us at 2M): the three best only decrease
 // from FLT_MAX, and every NaN pattern -- and +inf -- is above FLT_MAX as an unsigned integer, so such a
 // d leaves them unchanged exactly as the reference's `dist < best` (false for NaN and inf) does.
-#ifndef HIDEGS_KNN_NAN_CHECK
-#define HIDEGS_KNN_NAN_CHECK 0
-#endif
 __device__ __forceinline__ void kbest(float d, float& b0, float& b1, float& b2)
 {
-    const uint32_t x = (!HIDEGS_KNN_NAN_CHECK || d == d) ? __float_as_uint(d) : __float_as_uint(FLT_MAX);
+    const uint32_t x = __float_as_uint(d);
     const uint32_t c0 = __float_as_uint(b0), c1 = __float_as_uint(b1), c2 = __float_as_uint(b2);
     const uint32_t t0 = min(c0, x), u0 = max(c0, x);
     const uint32_t t1 = min(c1, u0), u1 = max(c1, u0);
@@ -122,6 +108,8 @@ __device__ __forceinline__ float uniform_lane(float v, int src)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
+constexpr int kChunk = kLeaf / kSub;  // points per sub-box
+
 // Evaluates the kChunk candidates held by lanes k0 .. k0 + kChunk of `c` (one point per lane) against
 // query p: each candidate is broadcast with v_readlane into scalar registers, so the loop has no
 // memory latency at all.  Candidates at or past `nvalid` and the query itself (lane `self`) enter as
@@ -130,30 +118,11 @@ __device__ __forceinline__ void eval_lanes(float4 c, int k0, int nvalid, int sel
                                            float& b2)
 {
 #pragma unroll
-    for (int j = 0; j < 16; j++) {
+    for (int j = 0; j < kChunk; j++) {
         const int k = k0 + j;
         const float4 q = make_float4(uniform_lane(c.x, k), uniform_lane(c.y, k), uniform_lane(c.z, k), 0.f);
         const float d = sqdist(p, q);
         kbest((k < nvalid && k != self) ? d : FLT_MAX, b0, b1, b2);
-    }
-}
-
-// Evaluates kChunk staged candidates stage[k0 .. k0 + kChunk) against query p.  All LDS reads and
-// distances are independent and issued first; only the insertion chain is serial.  Candidates at
-// or past `nvalid` and the query itself (index `self`) enter as FLT_MAX, which leaves the three
-// best unchanged exactly as skipping them would.
-constexpr int kChunk = 16;
-__device__ __forceinline__ void eval_chunk(const float4* stage, int k0, int nvalid, int self, float4 p, float& b0,
-                                           float& b1, float& b2)
-{
-#pragma unroll
-    for (int h = 0; h < kChunk; h += kChunk / 2) {
-        float d[kChunk / 2];
-#pragma unroll
-        for (int j = 0; j < kChunk / 2; j++) d[j] = sqdist(p, stage[k0 + h + j]);
-#pragma unroll
-        for (int j = 0; j < kChunk / 2; j++)
-            kbest((k0 + h + j < nvalid && k0 + h + j != self) ? d[j] : FLT_MAX, b0, b1, b2);
     }
 }
 
@@ -258,14 +227,6 @@ __global__ __launch_bounds__(kBlock) void morton_kernel(const float* __restrict_
 }
 
 // ---- 3./4. gather into sorted order; leaf and super boxes ---------------------------------------
-__device__ __forceinline__ Box wave_box(float4 p, bool valid)
-{
-    Box b;
-    b.lo = make_float4(wave_min(valid ? p.x : FLT_MAX), wave_min(valid ? p.y : FLT_MAX), wave_min(valid ? p.z : FLT_MAX), 0.f);
-    b.hi = make_float4(wave_max(valid ? p.x : -FLT_MAX), wave_max(valid ? p.y : -FLT_MAX), wave_max(valid ? p.z : -FLT_MAX), 0.f);
-    return b;
-}
-
 // Leaf L's box and its kSub sub-boxes of kLeaf / kSub consecutive points (the fine filter), from the
 // wave holding the leaf's points (lane = point in leaf).
 __device__ __forceinline__ void store_leaf_boxes(const float4 p, const bool valid, const int L, const int lane,
@@ -293,14 +254,9 @@ __device__ __forceinline__ void store_leaf_boxes(const float4 p, const bool vali
     if (lane == 0) leaves[L] = Box{make_float4(v[0], v[1], v[2], 0.f), make_float4(v[3], v[4], v[5], 0.f)};
 }
 
-#ifndef HIDEGS_KNN_FUSED_BOX
-#define HIDEGS_KNN_FUSED_BOX 1  // the gather also writes the leaf and sub-boxes (0: a leaf_box launch rereads the
-                                // sorted array): distCUDA2 frustum 1143/1146 -> 1138/1125 us, uniform 1066/1063 -> 1056/1026
-#endif
-// Sorted point j = original point order[j] as {x, y, z, bits(original index)}.  With Boxes, wave w of
-// block b holds leaf 4b + w (kLeaf == kWave) and also writes its boxes: the reductions of
-// leaf_box_kernel on the same values, so the same bits, without reading the sorted array again.
-template <bool Boxes>
+// Sorted point j = original point order[j] as {x, y, z, bits(original index)}.  Wave w of block b holds
+// leaf 4b + w (kLeaf == kWave) and also writes its boxes, without reading the sorted array again (a
+// launch of its own for the boxes: distCUDA2 frustum 1138/1125 -> 1143/1146 us, uniform 1056/1026 -> 1066/1063).
 __global__ __launch_bounds__(kBlock) void gather_kernel(const float* __restrict__ pts, const uint32_t* __restrict__ order,
                                                         int P, float4* __restrict__ sp, int nleaves,
                                                         Box* __restrict__ leaves, Box* __restrict__ subs)
@@ -317,21 +273,9 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const float* __restrict_
             valid = true;
         }
     }
-    if (!Boxes) return;
     const int L = j / kLeaf;  // wave-uniform
     if (L >= nleaves) return;  // whole wave
     store_leaf_boxes(p, valid, L, lane_id(), leaves, subs);
-}
-
-__global__ __launch_bounds__(kBlock) void leaf_box_kernel(const float4* __restrict__ sp, int P, int nleaves,
-                                                          Box* __restrict__ leaves, Box* __restrict__ subs)
-{
-    const int L = blockIdx.x * kWaves + threadIdx.x / kWave;
-    if (L >= nleaves) return;
-    const int lane = lane_id();
-    const int i = L * kLeaf + lane;
-    const bool valid = i < P;
-    store_leaf_boxes(valid ? sp[i] : make_float4(0.f, 0.f, 0.f, 0.f), valid, L, lane, leaves, subs);
 }
 
 __global__ __launch_bounds__(kBlock) void super_box_kernel(const Box* __restrict__ leaves, int nleaves, int nsuper,
@@ -349,45 +293,17 @@ __global__ __launch_bounds__(kBlock) void super_box_kernel(const Box* __restrict
 }
 
 // ---- 5. phase 1: one wave per leaf ------------------------------------------------------------
-#ifndef HIDEGS_KNN_GROUPS
-#define HIDEGS_KNN_GROUPS 2
-#endif
-constexpr int kGroups = HIDEGS_KNN_GROUPS;  // query groups per wave for the coarse filter
-#ifndef HIDEGS_KNN_SUPER_BATCH
-#define HIDEGS_KNN_SUPER_BATCH 2
-#endif
-#ifndef HIDEGS_KNN_LEAF_BATCH
-#define HIDEGS_KNN_LEAF_BATCH 2
-#endif
-constexpr int kSuperBatch = HIDEGS_KNN_SUPER_BATCH;  // super-boxes tested per lane per batch
-constexpr int kLeafBatch = HIDEGS_KNN_LEAF_BATCH;    // passing super-boxes whose leaf boxes load together
-constexpr int kListCap = 256;               // candidate leaves buffered per wave
-#ifndef HIDEGS_KNN_FLUSH_BATCH
-#define HIDEGS_KNN_FLUSH_BATCH 4
-#endif
-constexpr int kFlushBatch = HIDEGS_KNN_FLUSH_BATCH;  // candidate leaves loaded together
+constexpr int kGroups = 2;      // query groups per wave for the coarse filter (4 and 8: more box tests, slower)
+constexpr int kSuperBatch = 2;  // super-boxes tested per lane per batch
+constexpr int kLeafBatch = 2;   // passing super-boxes whose leaf boxes load together
+constexpr int kListCap = 256;   // candidate leaves buffered per wave
+constexpr int kFlushBatch = 4;  // candidate leaves loaded together
 constexpr int kGroupLanes = kWave / kGroups;
-#ifndef HIDEGS_KNN_SUBBOX_FILTER
-#define HIDEGS_KNN_SUBBOX_FILTER 1  // 0: no per-lane sub-box test before the point filter (A/B builds)
-#endif
-#ifndef HIDEGS_KNN_BAILOUT
-#define HIDEGS_KNN_BAILOUT 256
-#endif
-constexpr int kBailout = HIDEGS_KNN_BAILOUT;  // candidate leaves after which a wave hands its queries to phase 2
-#ifndef HIDEGS_KNN_SEED_NEIGHBORS
-#define HIDEGS_KNN_SEED_NEIGHBORS 1  // 0: seed from the own leaf only (A/B builds)
-#endif
-#ifndef HIDEGS_KNN_SEED_FILTER
-#define HIDEGS_KNN_SEED_FILTER 1  // neighbour seeds through the group point filter (0: all 128 evaluated):
-                                  // knn_leaf frustum 836/831 -> 815/814 us, uniform 784/787 -> 773/765 (2M)
-#endif
-#ifndef HIDEGS_KNN_SCALAR_SUBS
-#define HIDEGS_KNN_SCALAR_SUBS 1  // sub-boxes by scalar loads (0: vector loads + readlanes): 893 -> 840 us frustum,
-                                  // 848 -> 787 uniform, 448 -> 492 plane (2M points)
-#endif
-#ifndef HIDEGS_KNN_POINT_FILTER
-#define HIDEGS_KNN_POINT_FILTER 1  // 0: evaluate whole passing sub-boxes (A/B builds, tools/build_variant.py)
-#endif
+constexpr int kBailout = 256;   // candidate leaves after which a wave hands its queries to phase 2
+// The walk appends a leaf box test's `cnt` passing leaves to the list only while the list's total stays
+// at or below kBailout, and bails otherwise.  So the list never holds more than kBailout <= kListCap
+// leaves: it needs no emptying during the walk, and is filled once and evaluated once after it.
+static_assert(kBailout <= kListCap, "the candidate list holds every leaf a wave that does not bail passes");
 
 // Boxes of the active queries of each group of kGroupLanes lanes, broadcast to every lane.
 __device__ __forceinline__ void group_boxes(float4 p, bool active, float4 (&lo)[kGroups], float4 (&hi)[kGroups])
@@ -422,28 +338,37 @@ __device__ __forceinline__ void group_bounds(float b2, bool active, float (&ub)[
 
 // ---- phase 1 kernel ------------------------------------------------------------
 struct KnnCounters {
-    uint32_t hard;             // number of queries sent to phase 2
-    uint32_t pad;
-    unsigned long long coarse;  // phase 1: candidate leaves passing the wave-level test
-    unsigned long long fine;    // phase 1: candidate sub-boxes evaluated
-    uint32_t max_coarse, max_fine;
-    uint32_t hist[8];           // waves by coarse leaves: <16, <32, <64, <128, <256, <512, <1024, more
+    uint32_t hard;  // number of queries sent to phase 2
 };
+static_assert(sizeof(KnnCounters) <= kAlign, "knn_stats.h finds its block one carving step behind the counters");
 
-#ifndef HIDEGS_KNN_WAVES
-#define HIDEGS_KNN_WAVES 7  // waves per SIMD the phase-1 register budget is set for (72 VGPRs, 6 spilled to
-                           // scratch, 28 B per lane): knn_leaf 792/790 -> 773/773 us frustum against
-                           // the 6 that 79 VGPRs gave (profiles/r04_knn_waves.md)
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_KNN_WAVES))) void knn_leaf_kernel(const float4* __restrict__ sp, int P, int nleaves, int nsuper,
+// Mask of the lanes below `lane`: its popcount with a ballot is the lane's rank among the set lanes.
+__device__ __forceinline__ uint64_t lanes_below(int lane) { return (lane == 0) ? 0ull : (~0ull >> (64 - lane)); }
+
+// Appends query `me` of every lane with `flag` to the hard list (phase 2's input): one atomic per wave.
+__device__ __forceinline__ void push_hard(bool flag, int me, KnnCounters* __restrict__ counters,
+                                          uint32_t* __restrict__ hard)
+{
+    const uint64_t m = __ballot(flag);
+    if (!m) return;
+    const int lane = lane_id();
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&counters->hard, (uint32_t)__popcll(m));
+    base = __shfl(base, 0, kWave);
+    if (flag) hard[base + __popcll(m & lanes_below(lane))] = (uint32_t)me;
+}
+
+// At least 7 waves per SIMD set the register budget: knn_leaf 792/790 -> 773/773 us frustum against the 6
+// waves that the 79 VGPRs of a free allocation gave (profiles/r04_knn_waves.md).  The kernel now takes 64
+// VGPRs and no scratch, so 8 waves fit (profiles/r08_knn_refactor.md).
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7))) void knn_leaf_kernel(const float4* __restrict__ sp, int P, int nleaves, int nsuper,
                                                           const Box* __restrict__ leaves, const Box* __restrict__ subs,
                                                           const Box* __restrict__ supers,
                                                           float* __restrict__ out, uint32_t* __restrict__ hard,
-                                                          KnnCounters* __restrict__ counters,
-                                                          unsigned long long* __restrict__ trace, int stats)
+                                                          KnnCounters* __restrict__ counters)
 {
     __shared__ uint32_t s_list[kWaves][kListCap];
-    const unsigned long long t_start = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    WaveStats ws;  // statistics builds only (knn_stats.h): empty otherwise
     const int wave = threadIdx.x / kWave;
     const int lane = lane_id();
     const int L = xcd_swizzle(blockIdx.x, gridDim.x) * kWaves + wave;
@@ -454,19 +379,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
     const float4 p = valid ? sp[me] : make_float4(0.f, 0.f, 0.f, 0.f);
     float b0 = FLT_MAX, b1 = FLT_MAX, b2 = FLT_MAX;
 
-    // seed from the own leaf and, with HIDEGS_KNN_SEED_NEIGHBORS, its two Morton neighbours (a query
-    // near its leaf's border finds a tight bound there, which prunes the box walk below)
+    // seed from the own leaf and its two Morton neighbours (a query near its leaf's border finds a
+    // tight bound there, which prunes the box walk below)
     {
         const int nc = min(kLeaf, P - L * kLeaf);
         for (int k0 = 0; k0 < nc; k0 += kChunk) eval_lanes(p, k0, nc, lane, p, b0, b1, b2);
-#if HIDEGS_KNN_SEED_NEIGHBORS
         const int ln = L - 1, rn = L + 1;
         const float4 pl = ln >= 0 ? sp[ln * kLeaf + lane] : p;
         const float4 pr = rn < nleaves ? sp[min(rn * kLeaf + lane, P - 1)] : p;
-#if HIDEGS_KNN_SEED_FILTER
         // A neighbour point is evaluated only if it lies within some query group's bound of that
         // group's box (boxes and bounds over every valid lane, so each lane's three best come out
-        // exactly as from evaluating all 64: a skipped point is at least its bound from every query)
+        // exactly as from evaluating all 64: a skipped point is at least its bound from every query).
+        // All 128 evaluated instead: knn_leaf frustum 815/814 -> 836/831 us, uniform 773/765 -> 784/787 (2M).
         float4 slo[kGroups], shi[kGroups];
         float sub[kGroups];
         group_boxes(p, valid, slo, shi);
@@ -484,18 +408,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
             }
         };
         if (ln >= 0) seed_filtered(pl, kLeaf);
-        if (rn < nleaves) {
-            seed_filtered(pr, min(kLeaf, P - rn * kLeaf));
-        }
-#else
-        if (ln >= 0)
-            for (int k0 = 0; k0 < kLeaf; k0 += kChunk) eval_lanes(pl, k0, kLeaf, -1, p, b0, b1, b2);
-        if (rn < nleaves) {
-            const int nr = min(kLeaf, P - rn * kLeaf);
-            for (int k0 = 0; k0 < nr; k0 += kChunk) eval_lanes(pr, k0, nr, -1, p, b0, b1, b2);
-        }
-#endif
-#endif
+        if (rn < nleaves) seed_filtered(pr, min(kLeaf, P - rn * kLeaf));
     }
 
     // outliers -> phase 2
@@ -505,14 +418,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
         const float nfin = (float)__popcll(__ballot(finite));
         const float mean = wave_sum(finite ? b2 : 0.f) / fmaxf(nfin, 1.f);
         const bool is_hard = valid && (!finite || b2 > kHardFactor * mean);
-        const uint64_t hm = __ballot(is_hard);
-        if (hm) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&counters->hard, (uint32_t)__popcll(hm));
-            base = __shfl(base, 0, kWave);
-            const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-            if (is_hard) hard[base + __popcll(hm & lt)] = (uint32_t)me;
-        }
+        push_hard(is_hard, me, counters, hard);
         active = valid && !is_hard;
     } else {
         active = false;  // a single leaf holds every point: the seed is the answer
@@ -521,98 +427,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
     }
 
     if (__ballot(active)) {
-        // Coarse filter against kGroups query groups (16 Morton-consecutive queries each, so a
+        // Coarse filter against kGroups query groups (32 Morton-consecutive queries each, so a
         // leaf that straddles a Morton jump does not inflate one wave-wide box): a box passes
         // if it is within the group's upper bound of some group's box.  The walk is organised
         // for memory-level parallelism: super-boxes are tested kSuperBatch per lane at a time,
         // the leaf boxes of kLeafBatch passing super-boxes are loaded together, passing leaves
-        // go to an LDS list, and the list is evaluated with the next leaves' points and
-        // sub-boxes already in flight.
+        // go to an LDS list, and after the walk the list is evaluated kFlushBatch leaves' loads
+        // at a time.
         float4 glo[kGroups], ghi[kGroups];
         float gub[kGroups];
         group_boxes(p, active, glo, ghi);
         group_bounds(b2, active, gub);
         uint32_t* list = s_list[wave];
         int nnear = 0, nfar = 0;  // list[0, nnear) near leaves, list[cap - nfar, cap) far leaves
-        int listed = 0;           // candidate leaves so far
         bool bail = false;
-        uint32_t n_coarse = 0, n_fine = 0;
-
-        // evaluate and empty the candidate list
-        auto flush = [&]() {
-            const int cnt = nnear + nfar;
-            const int nn = nnear;
-            auto at = [&](int i) { return (int)list[i < nn ? i : kListCap - 1 - (i - nn)]; };
-            // prefetch ring: point (all lanes) and sub-box halves (lanes < 2 kSub) of leaves i+1, i+2
-            // Batches of kFlushBatch leaves: every point and sub-box load of a batch is issued before
-            // any is used, so a batch costs one memory latency.  (A rotating prefetch across
-            // iterations measured no gain: the waitcnt pass drains all loads at the loop header.)
-            for (int i0 = 0; i0 < cnt; i0 += kFlushBatch) {
-                float4 pt[kFlushBatch], bx[kFlushBatch];
-                int Cb[kFlushBatch];
-#pragma unroll
-                for (int q = 0; q < kFlushBatch; q++) {
-                    Cb[q] = at(min(i0 + q, cnt - 1));
-                    pt[q] = sp[min(Cb[q] * kLeaf + lane, P - 1)];
-                    bx[q] = reinterpret_cast<const float4*>(subs + (size_t)Cb[q] * kSub)[lane & (2 * kSub - 1)];
-                }
-#pragma unroll
-                for (int q = 0; q < kFlushBatch; q++) {
-                    if (i0 + q >= cnt) break;
-                    n_coarse++;
-                    uint32_t smask4 = HIDEGS_KNN_SUBBOX_FILTER ? 0u : (1u << kSub) - 1u;
-#if HIDEGS_KNN_SCALAR_SUBS
-                    // the leaf's sub-boxes by scalar loads (the leaf index is wave-uniform): no readlanes
-                    const Box* sbp = subs + (size_t)__builtin_amdgcn_readfirstlane(Cb[q]) * kSub;
-#endif
-#pragma unroll
-                    for (int j = 0; j < kSub && HIDEGS_KNN_SUBBOX_FILTER; j++) {
-#if HIDEGS_KNN_SCALAR_SUBS
-                        const Box sb = sbp[j];
-#else
-                        const Box sb{make_float4(uniform_lane(bx[q].x, 2 * j), uniform_lane(bx[q].y, 2 * j),
-                                                 uniform_lane(bx[q].z, 2 * j), 0.f),
-                                     make_float4(uniform_lane(bx[q].x, 2 * j + 1), uniform_lane(bx[q].y, 2 * j + 1),
-                                                 uniform_lane(bx[q].z, 2 * j + 1), 0.f)};
-#endif
-                        if (__ballot(active && box_point_lb(sb, p) <= b2)) smask4 |= 1u << j;
-                    }
-                    const int nc = min(kLeaf, P - Cb[q] * kLeaf);
-#if HIDEGS_KNN_POINT_FILTER
-                    // point-level filter: lane c holds point c of the leaf; it is evaluated only if
-                    // its sub-box passed some lane's own bound AND it lies within some query group's
-                    // bound of that group's box (both skip only points that cannot improve any
-                    // active query's three best)
-                    uint64_t sm = 0;
-#pragma unroll
-                    for (int j = 0; j < kSub; j++)
-                        if (smask4 >> j & 1u) sm |= 0xFFFFull << (kChunk * j);
-                    bool usable = false;
-#pragma unroll
-                    for (int g = 0; g < kGroups; g++) usable |= box_point_lb(Box{glo[g], ghi[g]}, pt[q]) <= gub[g];
-                    uint64_t pm = __ballot(usable && lane < nc) & sm;
-                    n_fine += (uint32_t)__popcll(pm);
-                    while (pm) {
-                        const int k = __builtin_ctzll(pm);
-                        pm &= pm - 1;
-                        const float4 c = make_float4(uniform_lane(pt[q].x, k), uniform_lane(pt[q].y, k),
-                                                     uniform_lane(pt[q].z, k), 0.f);
-                        kbest(sqdist(p, c), b0, b1, b2);
-                    }
-#else
-                    while (smask4) {
-                        const int j = __builtin_ctz(smask4);
-                        smask4 &= smask4 - 1;
-                        n_fine++;
-                        eval_lanes(pt[q], j * kChunk, nc, -1, p, b0, b1, b2);
-                    }
-#endif
-                }
-                group_bounds(b2, active, gub);  // tighter group bounds for the next batch
-            }
-            nnear = nfar = 0;
-            group_bounds(b2, active, gub);
-        };
 
         for (int s0 = 0; s0 < nsuper; s0 += kWave * kSuperBatch) {
             uint64_t smask[kSuperBatch];
@@ -659,7 +487,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
                     if (q >= ns) break;
                     const int l = S[q] * kFan + lane;
                     bool lpass = false, near = false;
-                    if (l < nleaves && l != L && (!HIDEGS_KNN_SEED_NEIGHBORS || (l != L - 1 && l != L + 1))) {
+                    if (l < nleaves && l != L && l != L - 1 && l != L + 1) {  // those three were the seed
 #pragma unroll
                         for (int g = 0; g < kGroups; g++) {
                             const float d = box_box_lb(lb[q], glo[g], ghi[g]);
@@ -670,16 +498,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
                     const uint64_t lm = __ballot(lpass);
                     const int cnt = __popcll(lm);
                     if (cnt == 0) continue;
-                    listed += cnt;
-                    if (listed > kBailout) {  // a long-tail wave: its queries go to phase 2
+                    if (nnear + nfar + cnt > kBailout) {  // a long-tail wave: its queries go to phase 2
                         bail = true;
                         break;
                     }
-                    if (nnear + nfar + cnt > kListCap) flush();
                     // leaves touching a query group's box go to the front and are evaluated first,
                     // so the bounds shrink before the farther leaves are filtered
                     const uint64_t nm = __ballot(lpass && near), fm = lm & ~nm;
-                    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+                    const uint64_t lt = lanes_below(lane);
                     if (lpass && near) list[nnear + __popcll(nm & lt)] = (uint32_t)l;
                     if (lpass && !near) list[kListCap - 1 - nfar - __popcll(fm & lt)] = (uint32_t)l;
                     nnear += __popcll(nm);
@@ -694,31 +520,64 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HIDEGS_K
             // Waves whose coarse walk passes more than kBailout leaves (queries at the edge of a
             // sparse region inflate their group's bound) would run for milliseconds while the rest
             // of the grid idles; phase 2 searches each of their queries with its own bound instead.
-            const uint64_t am = __ballot(active);
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&counters->hard, (uint32_t)__popcll(am));
-            base = __shfl(base, 0, kWave);
-            const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-            if (active) hard[base + __popcll(am & lt)] = (uint32_t)me;
+            push_hard(active, me, counters, hard);
             active = false;
-        } else if (nnear + nfar) {
-            flush();
-        }
-        if (stats && lane == 0) {  // diagnostics only (HIDEGS_KNN_STATS): same-address atomics are slow
-            atomicAdd(&counters->coarse, (unsigned long long)n_coarse);
-            atomicAdd(&counters->fine, (unsigned long long)n_fine);
-            atomicMax(&counters->max_coarse, n_coarse);
-            atomicMax(&counters->max_fine, n_fine);
-            int bk = 0;
-            while (bk < 7 && n_coarse >= (16u << bk)) bk++;
-            atomicAdd(&counters->hist[bk], 1u);
-            if (trace) {
-                trace[4 * L + 0] = t_start;
-                trace[4 * L + 1] = __builtin_amdgcn_s_memrealtime();
-                trace[4 * L + 2] = n_coarse;
-                trace[4 * L + 3] = n_fine;
+            ws.bail();
+        } else {
+            // Evaluate the candidate list, near leaves first, in batches of kFlushBatch leaves: every
+            // point load of a batch is issued before any is used, so a batch costs one memory latency.
+            // (A rotating prefetch across iterations measured no gain: the waitcnt pass drains all
+            // loads at the loop header.)
+            const int cnt = nnear + nfar;
+            auto at = [&](int i) { return (int)list[i < nnear ? i : kListCap - 1 - (i - nnear)]; };
+            for (int i0 = 0; i0 < cnt; i0 += kFlushBatch) {
+                float4 pt[kFlushBatch];
+                int Cb[kFlushBatch];
+#pragma unroll
+                for (int q = 0; q < kFlushBatch; q++) {
+                    Cb[q] = at(min(i0 + q, cnt - 1));
+                    pt[q] = sp[min(Cb[q] * kLeaf + lane, P - 1)];
+                }
+#pragma unroll
+                for (int q = 0; q < kFlushBatch; q++) {
+                    if (i0 + q >= cnt) break;
+                    ws.leaf();
+                    // The leaf's sub-boxes by scalar loads (the leaf index is wave-uniform) instead of a vector
+                    // load and six readlanes each: 893 -> 840 us frustum, 848 -> 787 uniform, 448 -> 492 plane (2M).
+                    // Without this per-lane sub-box test before the point filter: frustum 889 -> 1003 us.
+                    const Box* sbp = subs + (size_t)__builtin_amdgcn_readfirstlane(Cb[q]) * kSub;
+                    uint32_t smask4 = 0u;
+#pragma unroll
+                    for (int j = 0; j < kSub; j++) {
+                        const Box sb = sbp[j];
+                        if (__ballot(active && box_point_lb(sb, p) <= b2)) smask4 |= 1u << j;
+                    }
+                    const int nc = min(kLeaf, P - Cb[q] * kLeaf);
+                    // point-level filter: lane c holds point c of the leaf; it is evaluated only if
+                    // its sub-box passed some lane's own bound AND it lies within some query group's
+                    // bound of that group's box (both skip only points that cannot improve any
+                    // active query's three best)
+                    uint64_t sm = 0;
+#pragma unroll
+                    for (int j = 0; j < kSub; j++)
+                        if (smask4 >> j & 1u) sm |= 0xFFFFull << (kChunk * j);
+                    bool usable = false;
+#pragma unroll
+                    for (int g = 0; g < kGroups; g++) usable |= box_point_lb(Box{glo[g], ghi[g]}, pt[q]) <= gub[g];
+                    uint64_t pm = __ballot(usable && lane < nc) & sm;
+                    ws.points(pm);
+                    while (pm) {
+                        const int k = __builtin_ctzll(pm);
+                        pm &= pm - 1;
+                        const float4 c = make_float4(uniform_lane(pt[q].x, k), uniform_lane(pt[q].y, k),
+                                                     uniform_lane(pt[q].z, k), 0.f);
+                        kbest(sqdist(p, c), b0, b1, b2);
+                    }
+                }
+                group_bounds(b2, active, gub);  // tighter group bounds for the next batch
             }
         }
+        ws.report(counters, L, lane);
     }
     if (active) out[__float_as_uint(p.w)] = ((b0 + b1) + b2) / 3.0f;
 }
@@ -806,6 +665,7 @@ struct KnnLayout {
     Box *leaves, *subs, *supers;
     uint32_t* hard;
     KnnCounters* counters;
+    size_t counter_bytes;
     float *partials, *params;
     size_t total;
 };
@@ -826,7 +686,10 @@ KnnLayout layout(void* base, int P)
     l.subs = c.take<Box>((size_t)nleaves * kSub);
     l.supers = c.take<Box>(nsuper);
     l.hard = c.take<uint32_t>(P);
+    const size_t counters_at = c.used;
     l.counters = c.take<KnnCounters>(1);
+    c.take<char>(knn_stats_bytes(nleaves));  // statistics builds: their block follows the counters (knn_stats.h)
+    l.counter_bytes = c.used - counters_at;  // zeroed before every call
     l.partials = c.take<float>(kBoundBlocks * 6);
     l.params = c.take<float>(8);
     l.total = c.used;
@@ -847,75 +710,27 @@ int dist_cuda2(hidegs_alloc_fn alloc, void* user, int P, const float* points, fl
     char* base = alloc(user, bytes);
     if (!base) return fail(HIDEGS_E_ALLOC, "distCUDA2: scratch allocation of " + std::to_string(bytes) + " bytes failed");
     const KnnLayout l = layout(base, P);
-    const char* stats_env = getenv("HIDEGS_KNN_STATS");
-    unsigned long long* trace = nullptr;
-    if (stats_env && *stats_env == '2') (void)hipMalloc(&trace, sizeof(unsigned long long) * 4 * ceil_div(P, kLeaf));
-    if (trace) (void)hipMemsetAsync(trace, 0, sizeof(unsigned long long) * 4 * ceil_div(P, kLeaf), stream);
     const int nleaves = ceil_div(P, kLeaf), nsuper = ceil_div(nleaves, kFan);
     const int nb = ceil_div(P, kBlock);
     const int nbound = std::min(kBoundBlocks, nb);
 
-    if (hipMemsetAsync(l.counters, 0, sizeof(KnnCounters), stream) != hipSuccess)
+    if (hipMemsetAsync(l.counters, 0, l.counter_bytes, stream) != hipSuccess)
         return fail(HIDEGS_E_HIP, "distCUDA2: memset failed");
     HIDEGS_LAUNCH("bounds", bounds_kernel, dim3(nbound), dim3(kBlock), 0, stream, points, P, l.partials);
     HIDEGS_LAUNCH("bounds_finalize", bounds_finalize_kernel, dim3(1), dim3(kBlock), 0, stream, l.partials, nbound, l.params);
     HIDEGS_LAUNCH("morton", morton_kernel, dim3(nb), dim3(kBlock), 0, stream, points, P, l.params, l.keys, l.vals);
-    int rc = sort_pairs_u64(l.sort_tmp, l.sort_bytes, l.keys, l.keys_sorted, l.vals, l.vals_sorted, P, kSortBegin,
+    int rc = sort_pairs_u64(l.sort_tmp, l.sort_bytes, l.keys, l.keys_sorted, l.vals, l.vals_sorted, P, 0,
                             3 * kMortonBits, stream);
     if (rc) return rc;
-    if (HIDEGS_KNN_FUSED_BOX) {
-        HIDEGS_LAUNCH("gather", gather_kernel<true>, dim3(nb), dim3(kBlock), 0, stream, points, l.vals_sorted, P, l.sp,
-                      nleaves, l.leaves, l.subs);
-    } else {
-        HIDEGS_LAUNCH("gather", gather_kernel<false>, dim3(nb), dim3(kBlock), 0, stream, points, l.vals_sorted, P, l.sp,
-                      nleaves, l.leaves, l.subs);
-        HIDEGS_LAUNCH("leaf_box", leaf_box_kernel, dim3(ceil_div(nleaves, kWaves)), dim3(kBlock), 0, stream, l.sp, P,
-                      nleaves, l.leaves, l.subs);
-    }
+    HIDEGS_LAUNCH("gather", gather_kernel, dim3(nb), dim3(kBlock), 0, stream, points, l.vals_sorted, P, l.sp, nleaves,
+                  l.leaves, l.subs);
     HIDEGS_LAUNCH("super_box", super_box_kernel, dim3(ceil_div(nsuper, kWaves)), dim3(kBlock), 0, stream, l.leaves, nleaves,
                        nsuper, l.supers);
     HIDEGS_LAUNCH("knn_leaf", knn_leaf_kernel, dim3(ceil_div(nleaves, kWaves)), dim3(kBlock), 0, stream, l.sp, P, nleaves,
-                       nsuper, l.leaves, l.subs, l.supers, mean_dists, l.hard, l.counters, trace,
-                  stats_env && *stats_env >= '1');
+                       nsuper, l.leaves, l.subs, l.supers, mean_dists, l.hard, l.counters);
     HIDEGS_LAUNCH("knn_hard", knn_hard_kernel, dim3(std::min(2048, ceil_div(nleaves, kWaves))), dim3(kBlock), 0, stream, l.sp,
                        P, nleaves, nsuper, l.leaves, l.supers, mean_dists, l.hard, l.counters);
-    if (trace) {
-        const int nl = ceil_div(P, kLeaf);
-        std::vector<unsigned long long> h(4 * (size_t)nl);
-        (void)hipMemcpyAsync(h.data(), trace, h.size() * 8, hipMemcpyDeviceToHost, stream);
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(trace);
-        unsigned long long t0 = ~0ull, t1 = 0;
-        std::vector<double> dur;
-        for (int i = 0; i < nl; i++)
-            if (h[4 * i + 1]) {
-                t0 = std::min(t0, h[4 * i]);
-                t1 = std::max(t1, h[4 * i + 1]);
-                dur.push_back((double)(h[4 * i + 1] - h[4 * i]));
-            }
-        std::sort(dur.begin(), dur.end());
-        auto pct = [&](double q) { return dur.empty() ? 0.0 : dur[(size_t)(q * (dur.size() - 1))] / 100.0; };
-        double sum = 0;
-        for (double d : dur) sum += d;
-        fprintf(stderr, "[hidegs knn trace] waves=%zu span=%.1f us sum=%.1f us avg-concurrency=%.1f "
-                "dur us p50=%.2f p90=%.2f p99=%.2f p999=%.2f max=%.2f\n", dur.size(), (t1 - t0) / 100.0, sum / 100.0,
-                sum / std::max(1.0, (double)(t1 - t0)), pct(0.5), pct(0.9), pct(0.99), pct(0.999), pct(1.0));
-        // start-time profile: waves started per 10% of the span
-        int bins[10] = {0};
-        for (int i = 0; i < nl; i++)
-            if (h[4 * i + 1]) bins[std::min(9, (int)(10.0 * (h[4 * i] - t0) / std::max(1ull, t1 - t0)))]++;
-        fprintf(stderr, "[hidegs knn trace] starts per tenth: %d %d %d %d %d %d %d %d %d %d\n", bins[0], bins[1],
-                bins[2], bins[3], bins[4], bins[5], bins[6], bins[7], bins[8], bins[9]);
-    }
-    if (const char* e = getenv("HIDEGS_KNN_STATS"); e && *e >= '1') {
-        KnnCounters h{};
-        if (hipMemcpyAsync(&h, l.counters, sizeof(h), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-            hipStreamSynchronize(stream) == hipSuccess)
-            fprintf(stderr, "[hidegs knn] P=%d leaves=%d supers=%d hard=%u coarse_leaves/wave=%.2f (max %u) "
-                    "sub_boxes/wave=%.2f (max %u) hist<16,32,64,128,256,512,1024,more: %u %u %u %u %u %u %u %u\n",
-                    P, nleaves, nsuper, h.hard, (double)h.coarse / nleaves, h.max_coarse, (double)h.fine / nleaves,
-                    h.max_fine, h.hist[0], h.hist[1], h.hist[2], h.hist[3], h.hist[4], h.hist[5], h.hist[6], h.hist[7]);
-    }
+    knn_stats_report(l.counters, P, nleaves, nsuper, stream);  // statistics builds only (knn_stats.h)
     return check_launch("distCUDA2", stream, 0);
 }
 

@@ -153,6 +153,20 @@ def test_frustum_100k_every_point(oracle_lib):
     assert_bits_equal(knn(pts), oracle_lib.knn_mean3(pts), "frustum 100k")
 
 
+def test_bail_out_wave_every_point(oracle_lib):
+    """A dense core (28,000 points = 437 leaves, sigma 0.01) at the centre of a sparse shell (12,000 points,
+    radius 50): the `core_shell` recipe of tools/knn_stress.py.  The core sits where the Morton octants meet,
+    so some leaves mix core and shell points; their query-group boxes then pass every core leaf, more than the
+    256 a wave lists, and the wave hands its queries to phase 2.  Every point is checked.
+    `tools/knn_stats.py core_shell40k` (the statistics build) on this input: bailed=23 of 625 waves, hard=1502."""
+    g = np.random.default_rng(7)
+    core = g.normal(0, 0.01, (28_000, 3))
+    d = g.normal(size=(12_000, 3))
+    shell = 50 * d / np.linalg.norm(d, axis=1, keepdims=True)
+    pts = np.concatenate([core, shell]).astype(np.float32)
+    assert_bits_equal(knn(pts), oracle_lib.knn_mean3(pts), "core in shell 40k")
+
+
 def test_sfm_like_200k_sampled(oracle_lib):
     pts = sfm_like(200_000)
     got = knn(pts)

@@ -24,6 +24,14 @@ import simple_knn  # noqa: E402
 SHAPES = ("box", "blobs", "plane", "line", "lattice", "duplicates", "outliers", "core_shell", "frustum")
 
 
+def core_shell(g, n_core, n_shell):
+    """A dense core (sigma 0.01) at the centre of a sparse shell of radius 50."""
+    core = g.normal(0, 0.01, (n_core, 3))
+    d = g.normal(size=(n_shell, 3))
+    shell = 50 * d / np.linalg.norm(d, axis=1, keepdims=True)
+    return np.concatenate([core, shell]).astype(np.float32)
+
+
 def make(g, shape, n):
     if shape == "box":
         scale = 10.0 ** g.uniform(-3, 3)
@@ -55,11 +63,7 @@ def make(g, shape, n):
         p[g.choice(n, m, replace=False)] = g.uniform(-1e5, 1e5, (m, 3))
         return p
     if shape == "core_shell":
-        k = n // 2
-        core = g.normal(0, 0.01, (k, 3))
-        d = g.normal(size=(n - k, 3))
-        shell = 50 * d / np.linalg.norm(d, axis=1, keepdims=True)
-        return np.concatenate([core, shell]).astype(np.float32)
+        return core_shell(g, n // 2, n - n // 2)
     z = g.uniform(2, 20, n)  # frustum
     tx = np.tan(np.radians(30.0))
     return np.c_[g.uniform(-0.95, 0.95, n) * tx * z, g.uniform(-0.95, 0.95, n) * tx * 0.5625 * z, z].astype(np.float32)

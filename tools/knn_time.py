@@ -10,6 +10,7 @@ import torch  # noqa: E402
 import simple_knn  # noqa: E402
 from hidegs_amd import _lib, synthetic  # noqa: E402
 
+torch.manual_seed(0)  # the same sets in every process: builds are compared across runs
 sets = {"frustum2M": synthetic.frustum_points(2_000_000), "uniform2M": torch.rand(2_000_000, 3),
         "plane2M": torch.cat([torch.rand(2_000_000, 2), torch.zeros(2_000_000, 1)], 1)}
 for name, pts in sets.items():
@@ -24,7 +25,7 @@ for name, pts in sets.items():
         e1.record()
         torch.cuda.synchronize()
         tot.append(e0.elapsed_time(e1) * 1e3)
-    per = {k: [] for k in ("knn_leaf", "knn_hard", "radix_scatter_u64", "gather", "leaf_box")}
+    per = {k: [] for k in ("knn_leaf", "knn_hard", "radix_scatter_u64", "gather")}
     for _ in range(10):
         with _lib.kernel_timer() as kt:
             simple_knn._C.distCUDA2(p)

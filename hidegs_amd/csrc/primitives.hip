@@ -117,7 +117,9 @@ constexpr int kMaxSegmentBits = 16;        // segmented path: at most 65536 segm
 constexpr long long kSegmentedMinN = 65536;  // below this the plain LSD passes are cheaper
 constexpr long long kSegmentedMinAvg = 64;   // pairs per segment on average, else the plain passes: one
                                              // workgroup per ~30-pair segment (distCUDA2's 48-bit Morton
-                                             // keys of 2M points) costs more than the 4 low-digit passes
+                                             // keys of 2M points) costs more than the 4 low-digit passes;
+                                             // with its 16 segment bits distCUDA2 turns segmented at
+                                             // 64 << 16 = 4,194,304 points
 constexpr long long kTileSegmentedMinAvg = 8;  // the same for hidegs_sort_tile_pairs, per tile of the caller's grid: small
                                                // views (config 2, 100k Gaussians) took 6 plain passes, 105-115 us, against
                                                // 68-70 us segmented (64 / 32 / 16 / 8 / 1 A/B in DESIGN.md, "Small views")

@@ -5,7 +5,8 @@ same order (explicit fmaf, -ffp-contract=off on both sides, ((b0+b1)+b2)/3.0f), 
 result must be bit-identical (compared as uint32 bit patterns; inf and FLT_MAX/3 included).
 Sizes: every point checked up to 100k; at 2M a seeded sample of queries is checked against
 all 2M points, plus size-independent properties (permutation equivariance, exact scaling by
-powers of two).
+powers of two); at 4,194,304 points, where the Morton sort changes implementation, every cloud
+point is checked against the run that sorts the other way.
 """
 import os
 
@@ -211,3 +212,42 @@ def test_config5_scale_10m_sampled(oracle_lib):
     assert got.shape == (10_000_000,) and np.isfinite(got).all() and (got >= 0).all()
     idx = np.random.default_rng(10).choice(len(pts), 256, replace=False)
     assert_bits_equal(got[idx], oracle_lib.knn_mean3_subset(pts, idx), "frustum 10M sample")
+
+
+@pytest.mark.parametrize("cloud", ["uniform", "hot"])
+def test_both_sort_paths_give_the_same_result_on_every_point(oracle_lib, cloud):
+    """distCUDA2 on either side of the point count where its Morton sort changes implementation
+    (hidegs_sort_pairs_u64 over [0, 48): segmented from 64 << 16 = 4,194,304 points, six plain passes
+    below), every cloud point compared.  pts = [cloud, pins, X] with P = 4,194,304 (test_sort_cases.knn_case):
+    distCUDA2(pts) sorts segmented, distCUDA2(pts[:-1]) plain -- asserted from the launch counts -- and
+    the results of all P - k cloud points must be bit-identical (k = 3 / 9 <= 16: only the pins and X are
+    left out).  Dropping X changes no cloud point's answer: the pins fix the bounding box, and X is
+    farther from every cloud point than the cloud's diameter, so it is among nobody's three nearest.
+      uniform  the unit cube between pins at z = -4 and 4: 8420 segments, the largest 601 pairs;
+      hot      sfm_like without outliers inside 8 corner pins at +-2000: 8 segments of 350K .. 1.07M
+               pairs hold over 99.9 % of the points -- the partition queue several records deep.
+    The segmented result is also tied to the definition: 5000 sampled queries, the pins and X against the
+    brute-force oracle (each against all P points: 10.7-11.0 s of host time on 8 threads)."""
+    import test_sort_cases as cases
+    from hidegs_amd import _lib, primitives
+    case = cases.knn_case(cloud)
+    cases.check_knn_case(cloud, case)
+    pts, k = case[0], case[1]
+    P = len(pts)
+    assert P == 64 << 16 and k <= 16
+
+    def run(p):
+        primitives.queue_error(clear=True)
+        with _lib.kernel_timer() as kt:
+            out = knn(p)
+        assert primitives.queue_error() == 0
+        return out, kt.get("segment_sort")[1], kt.get("radix_hist_u64")[1]
+
+    seg, seg_launches, seg_hists = run(pts.copy())  # the shared points stay read-only
+    assert (seg_launches, seg_hists) == (1, 2), "P points did not take the segmented sort"
+    plain, plain_launches, plain_hists = run(pts[:-1].copy())
+    assert (plain_launches, plain_hists) == (0, 6), "P - 1 points did not take the plain passes"
+    assert_bits_equal(seg[: P - k], plain[: P - k], f"{cloud}: segmented against plain sort")
+    idx = np.random.default_rng(12).choice(P - k, 5000, replace=False)
+    idx = np.concatenate([idx, np.arange(P - k, P)])
+    assert_bits_equal(seg[idx], oracle_lib.knn_mean3_subset(pts, idx), f"{cloud}: segmented against the oracle")

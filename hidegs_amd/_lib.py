@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/hidegs.h (hidegs_amd/libhidegs.so).
+"""ctypes binding of the C ABI in include/hidegs.h and include/hidegs_rows.h (hidegs_amd/libhidegs.so).
 
 This is the only place that loads the native library.  It fails loudly: a missing
 library raises ImportError-like RuntimeError at first use, and a non-zero return
@@ -81,18 +81,32 @@ SIGNATURES = {
     "hidegs_version": (C.c_char_p, []),
 }
 
+
+class RowField(C.Structure):
+    """hidegs_row_field (include/hidegs_rows.h)."""
+    _fields_ = [("rows", C.c_void_p), ("packed", C.c_void_p), ("n_rows", C.c_longlong), ("width", C.c_int)]
+
+
+# include/hidegs_rows.h, in its order
+ROW_SIGNATURES = {
+    "hidegs_select_scratch_bytes": (SZ, [LL]),
+    "hidegs_select_flagged": (I, [P, SZ, P, LL, P, P, P]),
+    "hidegs_gather_rows": (I, [P, I, P, LL, P]),
+    "hidegs_scatter_rows": (I, [P, I, P, LL, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
 
 def load_library(path: str) -> C.CDLL:
-    """A build of the ABI at `path` with every signature of include/hidegs.h bound (lib() for the
-    product build; tests load the build.VARIANTS this way)."""
+    """A build of the ABI at `path` with every signature of include/hidegs.h and include/hidegs_rows.h
+    bound (lib() for the product build; tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
                            "(or __graft_entry__.build()) to compile it for gfx950")
     dll = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,4 +1,4 @@
-"""Build recipe for hidegs_amd/libhidegs.so (the C-ABI library of include/hidegs.h).
+"""Build recipe for hidegs_amd/libhidegs.so (the C-ABI library of include/hidegs.h and include/hidegs_rows.h).
 
 Built in-tree with hipcc for gfx950 so the .so travels to the GPU box with the
 repository snapshot.  `python -m hidegs_amd.build` or `__graft_entry__.build()`.
@@ -26,9 +26,10 @@ INCLUDE = os.path.join(HERE, "..", "include")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhidegs.so")
 VARIANT_DIR = os.path.join(HERE, "variants")
-SOURCES = ["abi.cpp", "timing.cpp", "primitives.hip", "knn.hip", "adam.hip", "wire.hip"]
+SOURCES = ["abi.cpp", "timing.cpp", "primitives.hip", "knn.hip", "adam.hip", "wire.hip", "rows.hip"]
 # every header: a change to any of them rebuilds every object
-HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "hidegs.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "hidegs.h"),
+                                                         os.path.join(INCLUDE, "hidegs_rows.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf, so the
 # oracle (oracle/knn_ref.c) can reproduce each rounding step bit for bit.

@@ -1,4 +1,5 @@
-"""Torch-facing wrappers of the binning primitives in include/hidegs.h.
+"""Torch-facing wrappers of the binning primitives in include/hidegs.h, and of the stream compaction
+of include/hidegs_rows.h.
 
 These are the stages between preprocess and render in Rasterizer::forward
 (rasterizer_impl.cu:321-371): inclusive scan of tiles_touched, the stable radix sort
@@ -44,6 +45,36 @@ def inclusive_scan_u32(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tenso
                                          _lib.stream_handle(dev))
         _lib.check(rc, "inclusive_scan_u32")
     return out
+
+
+def select_flagged(mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Stream compaction (include/hidegs_rows.h): the ascending positions of the non-zero entries of a
+    1-D bool / uint8 device mask.
+
+    Returns (indices, count): indices is int32 with mask.numel() entries of which the first `count` are
+    valid (the rest is uninitialised), count a 0-dim int32 device tensor.  The call does not synchronise;
+    reading `count` on the host does.
+    """
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 or not mask.is_contiguous():
+        raise RuntimeError(f"select_flagged: expected a contiguous 1-D bool or uint8 mask, got {mask.dtype} "
+                           f"of shape {tuple(mask.shape)}")
+    n = mask.numel()
+    if n >= 1 << 31:
+        raise RuntimeError("select_flagged: at most 2^31 - 1 entries")
+    if mask.device.type != "cuda":
+        raise RuntimeError(f"expected a GPU tensor, got one on {mask.device}")
+    dev = mask.device
+    with torch.cuda.device(dev):
+        indices = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return indices, torch.zeros((), dtype=torch.int32, device=dev)
+        count = torch.empty((), dtype=torch.int32, device=dev)
+        L = _lib.lib()
+        tmp = _scratch(L.hidegs_select_scratch_bytes(n), dev)
+        rc = L.hidegs_select_flagged(_lib.ptr(tmp), tmp.numel(), _lib.ptr(mask), n, _lib.ptr(indices),
+                                     count.data_ptr(), _lib.stream_handle(dev))
+        _lib.check(rc, "select_flagged")
+    return indices, count
 
 
 def sort_pairs(keys: torch.Tensor, values: torch.Tensor, begin_bit: int = 0,

@@ -25,6 +25,12 @@ reduced; rows outside the union are zero on every rank (the rasterizer's backwar
 zero rows for Gaussians it did not render), so the packed sum equals the dense one.
 Buckets of `bucket_bytes` (default 64 MiB) are all issued before any is waited on: a ring
 over xGMI is bound per link (~153 GB/s) and pays a fixed cost per collective.
+On device tensors the compaction runs on the library's kernels (csrc/rows.hip): the union's rows are
+selected on the device (`primitives.select_flagged`), their count is read once -- the one host
+synchronisation the compacted path keeps, because every rank must size the collectives alike -- and
+all fields are packed and, after the collectives, written back by one launch each
+(`wire.gather_rows` / `wire.scatter_rows`).  Host tensors (gloo) keep the torch ops that define it:
+sum, nonzero, index_select and index_copy_ per field.
 
 Backend: whatever process group is current -- "nccl" (RCCL on ROCm) on the GPU, "gloo" in
 the CPU tests.  Bitwise OR is formed from an all-gather of packed masks (RCCL has no
@@ -71,12 +77,12 @@ from __future__ import annotations
 
 import datetime
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Union
+from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
 import torch.distributed as dist
 
-from . import wire
+from . import primitives, wire
 
 LEAF_WIDTHS = {"xyz": 3, "f_dc": 3, "f_rest": 45, "opacity": 1, "scaling": 3, "rotation": 4}
 """Per-Gaussian fp32 widths of the HiDeGS leaf parameters (59 floats = 236 B; SURVEY §8(e) E1)."""
@@ -358,12 +364,21 @@ class ViewDPExchange:
         self._run_buckets(self._label_buckets([self._bucket(flat[s:s + per]) for s in range(0, flat.numel(), per)],
                                               what))
 
+    @staticmethod
+    def select_union(union: torch.Tensor) -> Tuple[torch.Tensor, int]:
+        """(rows, nu) of a device union mask: its set rows' ascending indices, int32, in the first nu
+        entries of `rows`.  Reading nu is the compacted path's one host synchronisation."""
+        rows, count = primitives.select_flagged(union.contiguous())
+        return rows, count.item()
+
     def sum_gradients(self, grads: Union[GradArena, Iterable[torch.Tensor]],
-                      union: Optional[torch.Tensor] = None) -> None:
+                      union: Optional[torch.Tensor] = None,
+                      selected: Optional[Tuple[torch.Tensor, int]] = None) -> None:
         """In-place SUM over ranks of per-Gaussian gradients (each (N, ...), same N).
 
         `union` (bool (N,), identical on every rank, rows visible to some rank) allows the
         compacted exchange; every row outside it must be zero on every rank.
+        `selected` is `select_union(union)` where the caller has already formed it (device tensors).
         """
         if isinstance(grads, GradArena):
             tensors, n = list(grads.views.values()), grads.n
@@ -394,11 +409,15 @@ class ViewDPExchange:
             self.last.union_rows = -1  # not counted: no host synchronisation on the one-rank path
             return
         rows = None
+        device = union is not None and union.is_cuda and all(g.is_cuda for g in tensors)
         if union is not None and n:
-            nu = int(union.sum())
+            if device:  # csrc/rows.hip: no union.sum(), no nonzero(); one read of the count
+                picked, nu = selected if selected is not None else self.select_union(union)
+            else:
+                nu = int(union.sum())
             self.last.union_rows = nu
             if nu < self.compact_below * n:
-                rows = union.nonzero().flatten()
+                rows = picked[:nu] if device else union.nonzero().flatten()
         else:
             self.last.union_rows = n
         if rows is None:
@@ -418,6 +437,12 @@ class ViewDPExchange:
             return
         widths = [g[0].numel() for g in tensors]
         packed = torch.empty(rows.numel() * sum(widths), dtype=torch.float32, device=tensors[0].device)
+        if device:  # every field in one launch each way, the same packed layout
+            fields = [g.view(n, w) for g, w in zip(tensors, widths)]
+            wire.gather_rows(fields, rows, packed)
+            self._all_reduce_buckets(packed, "compacted gradient")
+            wire.scatter_rows(fields, rows, packed)
+            return
         off = 0
         for g, w in zip(tensors, widths):
             torch.index_select(g.reshape(n, w), 0, rows, out=packed[off:off + rows.numel() * w].view(-1, w))
@@ -498,9 +523,16 @@ class ViewDPExchange:
         union, count = self.gather_visibility(visible)
         n = arena.n
         solo = self._solo()
-        nu = int(union.sum()) if n and not solo else 0  # (no host synchronisation on one rank)
+        selected = None
+        if solo or n == 0:  # (no host synchronisation on one rank)
+            nu = 0
+        elif union.is_cuda and arena.flat.is_cuda:  # selected once, handed down to sum_gradients
+            selected = self.select_union(union)
+            nu = selected[1]
+        else:
+            nu = int(union.sum())
         if solo or n == 0 or nu < self.compact_below * n:
-            self.sum_gradients(arena, union)
+            self.sum_gradients(arena, union, selected)
             optimizer.begin_step(union).run()  # counters advance only once the gradients are summed
         else:
             self.last.union_rows = nu

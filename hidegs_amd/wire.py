@@ -1,8 +1,15 @@
 """bf16 wire format of the view-DP exchange on the GPU (include/hidegs.h: hidegs_bf16_pack /
 _sum_ranks / _unpack; hidegs_amd/csrc/wire.hip).  Device tensors only: each call is one HBM pass on
 the tensors' device's current stream, bit-identical to the torch definition it replaces in
-view_dp._Bucket (the CPU path of that class keeps the torch ops for gloo ranks)."""
+view_dp._Bucket (the CPU path of that class keeps the torch ops for gloo ranks).
+
+gather_rows / scatter_rows (include/hidegs_rows.h; hidegs_amd/csrc/rows.hip) pack and unpack the rows of
+the compacted exchange: every field of the gradient arena in one launch, in the field-major packed
+layout [field][j][col] that index_select per field into consecutive slices gives."""
 from __future__ import annotations
+
+import ctypes as C
+from typing import List, Sequence
 
 import torch
 
@@ -94,3 +101,57 @@ def mask_union_count(bits: torch.Tensor, n: int):
                                                 _lib.ptr(count), _lib.stream_handle(dev))
     _lib.check(rc, "mask_union_count")
     return union, count
+
+
+def _row_fields(tensors: Sequence[torch.Tensor], rows: torch.Tensor, packed: torch.Tensor, what: str):
+    """(device, hidegs_row_field array, k): `tensors` against consecutive (k, w_i) slices of `packed`."""
+    tensors = list(tensors)
+    if rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous():
+        raise RuntimeError(f"{what}: rows must be a contiguous 1-D int32 tensor, got {rows.dtype}")
+    _need(packed, torch.float32, what)
+    k = rows.numel()
+    if k >= 1 << 31:
+        raise RuntimeError(f"{what}: at most 2^31 - 1 rows")
+    for t in tensors:
+        _need(t, torch.float32, what)
+        if t.dim() != 2 or t.size(1) < 1:
+            raise RuntimeError(f"{what}: every tensor must be (n, w) with w >= 1, got {tuple(t.shape)}")
+    total = k * sum(t.size(1) for t in tensors)
+    if packed.dim() != 1 or packed.numel() < total:
+        raise RuntimeError(f"{what}: the packed buffer must be flat and hold {total} values, got "
+                           f"{tuple(packed.shape)}")
+    dev = _lib.device_of(rows, packed, *tensors)
+    for t in (rows, packed, *tensors):
+        if t.device.type != "cuda":
+            raise RuntimeError(f"expected a GPU tensor, got one on {t.device}")
+    fields = (_lib.RowField * max(len(tensors), 1))()
+    off = 0
+    for f, t in zip(fields, tensors):
+        f.rows, f.n_rows, f.width = _lib.ptr(t), t.size(0), t.size(1)
+        f.packed = packed.data_ptr() + 4 * off if k else None
+        off += k * t.size(1)
+    return dev, fields, len(tensors), k
+
+
+def gather_rows(tensors: List[torch.Tensor], rows: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[field f][j] = tensors[f][rows[j]] for every f, as one launch per 8 tensors: `tensors` are
+    contiguous fp32 (n, w_f), `rows` int32 (k,), `out` a flat fp32 buffer of at least k * sum(w_f) values,
+    field-major ([field][j][col]).  A bit copy; a row index >= n is skipped."""
+    dev, fields, nf, k = _row_fields(tensors, rows, out, "gather_rows")
+    if k == 0 or nf == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _lib.lib().hidegs_gather_rows(C.cast(fields, C.c_void_p), nf, _lib.ptr(rows), k, _lib.stream_handle(dev))
+    _lib.check(rc, "gather_rows")
+    return out
+
+
+def scatter_rows(tensors: List[torch.Tensor], rows: torch.Tensor, packed: torch.Tensor) -> None:
+    """tensors[f][rows[j]] = packed[field f][j], the inverse of gather_rows on the same arguments; rows not
+    named keep their bits.  `rows` must be ascending and unique."""
+    dev, fields, nf, k = _row_fields(tensors, rows, packed, "scatter_rows")
+    if k == 0 or nf == 0:
+        return
+    with torch.cuda.device(dev):
+        rc = _lib.lib().hidegs_scatter_rows(C.cast(fields, C.c_void_p), nf, _lib.ptr(rows), k, _lib.stream_handle(dev))
+    _lib.check(rc, "scatter_rows")

@@ -29,7 +29,8 @@
  *   hidegs_bf16_pack / _sum_ranks / _unpack, hidegs_mask_pack / _union_count
  *                               <- no reference counterpart: local steps of the view-DP exchange
  *                                  (the reference trains on one GPU)
- * INTEGRATION.md shows the Python-side bindings.
+ * INTEGRATION.md shows the Python-side bindings.  Stream compaction and indexed row moves (hidegs_select_flagged,
+ * hidegs_gather_rows, hidegs_scatter_rows) are declared in hidegs_rows.h, next to this file.
  */
 #ifndef HIDEGS_H_INCLUDED
 #define HIDEGS_H_INCLUDED

@@ -176,9 +176,16 @@ __device__ __forceinline__ void set_digit(BigSeg& s, uint32_t lo, uint32_t hi)
     s.bits = (uint32_t)bits;
 }
 // digit of a pair of a record: bits [shift, shift + bits) of (low key half - lo)
-__device__ __forceinline__ uint32_t rec_digit(uint64_t key, uint32_t lo, int shift, uint32_t mask)
+__device__ __forceinline__ uint32_t rec_digit(uint32_t key_lo, uint32_t lo, int shift, uint32_t mask)
 {
-    return (((uint32_t)key - lo) >> shift) & mask;
+    return ((key_lo - lo) >> shift) & mask;
+}
+// The low half of keys[i], as a 4-byte load: what the phases that look at digits only (REDUCE, HIST) read.
+// segment_sort_kernel<true>'s scouts run them while the tile's own workgroup rewrites the high halves
+// (expand_records); the low halves keep their values.
+__device__ __forceinline__ uint32_t key_low(const uint64_t* keys, uint32_t i)
+{
+    return reinterpret_cast<const uint32_t*>(keys)[2 * (size_t)i];
 }
 
 // Chunk groups of a big record.  The SCATTER phase needs, per chunk and digit, the digit's count in
@@ -317,7 +324,7 @@ __device__ __forceinline__ uint32_t chunk_hist(const uint64_t* sk, const uint32_
 #pragma unroll
         for (int u = 0; u < U * kChunk / kBlock; u++) {
             const uint32_t i = i0 + t + u * kBlock;
-            dg[u] = i < cnt ? rec_digit(sk[base + i], lo, shift, mask) : ~0u;
+            dg[u] = i < cnt ? rec_digit(key_low(sk, base + i), lo, shift, mask) : ~0u;
         }
 #pragma unroll
         for (int u = 0; u < U * kChunk / kBlock; u++)

@@ -217,6 +217,9 @@ int sort_pairs(void* scratch, size_t scratch_bytes, const K* keys_in, K* keys_ou
     // segmented path: the segment ranges (the caller's tile ranges with ranges_out: tile ids
     // < num_tiles <= 2^(end_bit-32) leave no bits above end_bit, so segment == tile) and the
     // hot-tile queue (its job slots are cleared by the last histogram pass)
+    // with ranges_out the last pass hands segment_sort 8-byte {low key half, value} records in keys_out
+    // (the high half is the segment id); generic keys keep whole pairs: bits above end_bit survive
+    const bool packed = segmented && ranges_out != nullptr;
     int nseg = 0;
     uint32_t* seg_starts = nullptr;
     uint32_t* low_base = nullptr;
@@ -252,9 +255,19 @@ int sort_pairs(void* scratch, size_t scratch_bytes, const K* keys_in, K* keys_ou
         const bool last = p == lsd_passes - 1;
         uint4* zero_jobs = segmented && last ? reinterpret_cast<uint4*>(q.ctl) : nullptr;
         static_assert(Q_WORDS * sizeof(uint32_t) % kAlign == 0, "ctl and job slots contiguous");
-        HIDEGS_LAUNCH((sizeof(K) == 8 ? "radix_hist_u64" : "radix_hist_u32"), radix_hist_kernel<K>, dim3(nt),
-                      dim3(kBlock), 0, stream, src_k, n, shift, mask, nt, counts, zero_jobs,
-                      zero_jobs ? q.job_cap + Q_WORDS / 4 : 0u);
+        // records (radix.h): the first of two passes also writes the second one's digit as a byte per pair
+        // (into the value scratch), which is then all the second histogram reads
+        const bool rec_in = packed && lsd_passes == 2 && last, rec_digit_out = packed && lsd_passes == 2 && !last;
+        const int next_shift = shift + bits;
+        const uint32_t next_mask = rec_digit_out ? (1u << (span - bits)) - 1u : 0u;  // two passes: the other one's bits
+        const char* hist_name = sizeof(K) == 8 ? "radix_hist_u64" : "radix_hist_u32";
+        if (rec_in)
+            HIDEGS_LAUNCH(hist_name, (radix_hist_kernel<K, true>), dim3(nt), dim3(kBlock), 0, stream,
+                          reinterpret_cast<const K*>(src_v), n, shift, mask, nt, counts, zero_jobs,
+                          zero_jobs ? q.job_cap + Q_WORDS / 4 : 0u);
+        else
+            HIDEGS_LAUNCH(hist_name, radix_hist_kernel<K>, dim3(nt), dim3(kBlock), 0, stream, src_k, n, shift, mask, nt,
+                          counts, zero_jobs, zero_jobs ? q.job_cap + Q_WORDS / 4 : 0u);
         // digits above `mask` never occur: their (stale) totals only follow the used digits in the
         // scatter's exclusive scan, and their counts are never read
         const bool low = segmented && last && lsd_passes == 2;  // the previous pass's digit bases, for the starts
@@ -263,32 +276,43 @@ int sort_pairs(void* scratch, size_t scratch_bytes, const K* keys_in, K* keys_ou
         if (p < 2) pass_bits[p] = bits;
         // narrow digits (and, for the starts, a narrower previous pass: the passes are balanced, so
         // pass_bits[0] <= bits) take the smaller-LDS instance
-        const bool narrow = (int)mask < kNarrowRadix && n <= kNarrowMaxN;
-        if (segmented && last) {  // also the segments' first positions (no pass over the sorted keys)
-            const int b0 = lsd_passes == 2 ? pass_bits[0] : 0;
-            if (narrow && (1 << b0) <= kNarrowRadix)
-                HIDEGS_LAUNCH("radix_scatter_u64", (radix_scatter_kernel<K, true, kNarrowRadix>), dim3(nt), dim3(kSBlock),
-                              0, stream, src_k, src_v, dk, dv, n, shift, mask, nt, counts, totals, low_base, b0, seg_starts);
-            else
-                HIDEGS_LAUNCH("radix_scatter_u64", (radix_scatter_kernel<K, true>), dim3(nt), dim3(kSBlock), 0, stream,
-                              src_k, src_v, dk, dv, n, shift, mask, nt, counts, totals, low_base, b0, seg_starts);
-        } else if (narrow) {
-            HIDEGS_LAUNCH((sizeof(K) == 8 ? "radix_scatter_u64" : "radix_scatter_u32"),
-                          (radix_scatter_kernel<K, false, kNarrowRadix>), dim3(nt), dim3(kSBlock), 0, stream, src_k, src_v,
-                          dk, dv, n, shift, mask, nt, counts, totals, nullptr, 0, nullptr);
+        const bool with_starts = segmented && last;  // also the segments' first positions (no pass over the sorted keys)
+        const int b0 = with_starts && lsd_passes == 2 ? pass_bits[0] : 0;
+        const bool narrow = (int)mask < kNarrowRadix && n <= kNarrowMaxN && (1 << b0) <= kNarrowRadix;
+        const char* scatter_name = sizeof(K) == 8 ? "radix_scatter_u64" : "radix_scatter_u32";
+#define HIDEGS_SCATTER(...)                                                                                            \
+    HIDEGS_LAUNCH(scatter_name, (radix_scatter_kernel<K, __VA_ARGS__>), dim3(nt), dim3(kSBlock), 0, stream, src_k, src_v, \
+                  dk, dv, n, shift, mask, nt, counts, totals, with_starts ? low_base : nullptr, b0,                       \
+                  with_starts ? seg_starts : nullptr, next_shift, next_mask)
+        if (rec_in) {  // tile ids are whole high key halves (the caller's guarantee): 8-byte records
+            if (narrow) HIDEGS_SCATTER(true, kNarrowRadix, kOutRecords, true);
+            else HIDEGS_SCATTER(true, kRadix, kOutRecords, true);
+        } else if (rec_digit_out) {
+            if (narrow) HIDEGS_SCATTER(false, kNarrowRadix, kOutRecordsDigit);
+            else HIDEGS_SCATTER(false, kRadix, kOutRecordsDigit);
+        } else if (with_starts && packed) {  // one pass
+            if (narrow) HIDEGS_SCATTER(true, kNarrowRadix, kOutRecords);
+            else HIDEGS_SCATTER(true, kRadix, kOutRecords);
+        } else if (with_starts) {
+            if (narrow) HIDEGS_SCATTER(true, kNarrowRadix);
+            else HIDEGS_SCATTER(true, kRadix);
         } else {
-            HIDEGS_LAUNCH((sizeof(K) == 8 ? "radix_scatter_u64" : "radix_scatter_u32"), (radix_scatter_kernel<K, false>),
-                          dim3(nt), dim3(kSBlock), 0, stream, src_k, src_v, dk, dv, n, shift, mask, nt, counts, totals,
-                          nullptr, 0, nullptr);
+            if (narrow) HIDEGS_SCATTER(false, kNarrowRadix);
+            else HIDEGS_SCATTER(false, kRadix);
         }
+#undef HIDEGS_SCATTER
         src_k = dk;
         src_v = dv;
         shift += bits;
     }
     if (segmented) {
         uint64_t* ko = reinterpret_cast<uint64_t*>(keys_out);
-        HIDEGS_LAUNCH("segment_sort", segment_sort_kernel, dim3(nseg + kScouts), dim3(kBlock), 0, stream, ko,
-                      vals_out, seg_starts, ranges_out, nseg, q);
+        if (packed)
+            HIDEGS_LAUNCH("segment_sort", segment_sort_kernel<true>, dim3(nseg + kScouts), dim3(kBlock), 0, stream, ko,
+                          vals_out, seg_starts, ranges_out, nseg, q);
+        else
+            HIDEGS_LAUNCH("segment_sort", segment_sort_kernel<false>, dim3(nseg + kScouts), dim3(kBlock), 0, stream, ko,
+                          vals_out, seg_starts, ranges_out, nseg, q);
         HIDEGS_LAUNCH("big_segments", big_segment_kernel, dim3(kQueueBlocks), dim3(kBlock), 0, stream, ko, vals_out,
                       reinterpret_cast<uint64_t*>(alt_k), alt_v, q);
         // debug mode checks this call's queue itself (below); otherwise the last kernel hands a queue

@@ -63,7 +63,9 @@ __device__ __forceinline__ uint32_t digit_wave_prefix(uint32_t (*s_cnt)[kRadix])
 
 // counts[d * ntiles + tile] = number of keys of tile `tile` whose digit is d.
 // zero_jobs: zero_count 16-byte slots cleared on the side (the hot-tile queue's job slots).
-template <typename K>
+// Bytes: `keys` holds one digit byte per key instead (radix_scatter_kernel's kOutRecordsDigit output,
+// a tile's 4096 bytes as one 16-byte load per thread); shift is ignored.
+template <typename K, bool Bytes = false>
 __global__ __launch_bounds__(kBlock) void radix_hist_kernel(const K* __restrict__ keys, long long n, int shift,
                                                             uint32_t mask, int ntiles, uint32_t* __restrict__ counts,
                                                             uint4* __restrict__ zero_jobs, uint32_t zero_count)
@@ -81,7 +83,22 @@ __global__ __launch_bounds__(kBlock) void radix_hist_kernel(const K* __restrict_
     const int tile = xcd_swizzle(blockIdx.x, gridDim.x);
     const long long base = (long long)tile * kTile;
     K k[kItems];
-    if (sizeof(K) == 8 && base + kTile <= n && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
+    if (Bytes) {
+        const uint8_t* dg = reinterpret_cast<const uint8_t*>(keys);
+        static_assert(kItems == 16, "a thread's 16 digit bytes are one uint4");
+        if (base + kTile <= n && (reinterpret_cast<uintptr_t>(dg) & 15) == 0) {
+            const uint4 p = reinterpret_cast<const uint4*>(dg + base)[t];
+            const uint32_t w[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+            for (int j = 0; j < kItems; j++) atomicAdd(&s_hist[wave][(w[j / 4] >> (8 * (j % 4))) & mask], 1u);
+        } else {
+#pragma unroll
+            for (int j = 0; j < kItems; j++) {
+                const long long i = base + j * kBlock + t;
+                if (i < n) atomicAdd(&s_hist[wave][dg[i] & mask], 1u);
+            }
+        }
+    } else if (sizeof(K) == 8 && base + kTile <= n && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
         // full tile: 16-byte loads, two keys each (the histogram does not care about item order)
         const ulonglong2* k2 = reinterpret_cast<const ulonglong2*>(keys + base);
 #pragma unroll
@@ -220,9 +237,23 @@ __device__ __forceinline__ void segment_starts(const K (&k)[R], const bool (&ok)
 // 6 + 7 bits) 189 -> 183 us.  Only up to kNarrowMaxN pairs: the 4K frame's 42.9M pairs (7 + 8 bits)
 // went 880 -> 894 us with its 7-bit pass narrow -- a fourth workgroup's open digit runs cost more
 // once a pass's output no longer stays in the 256 MB MALL (profiles/r04_narrow_scatter.md).
+// Records (hidegs_sort_tile_pairs only, whose tile id is the whole high key half): between its kernels
+// the sort carries one 8-byte record {low key half, value} per pair instead of a 12-byte pair.
+//   Out == kOutRecords (with Starts, the last pass): the records go to keys_out at the pairs' final
+//     indices and vals_out is not written; segment_sort_kernel<true> knows the high half, the segment
+//     id, from starts[] and puts whole pairs back.
+//   Out == kOutRecordsDigit (the first of two passes): also each pair's digit of the NEXT pass
+//     (next_shift, next_mask), one byte per pair at vals_out, which is all the next histogram reads.
+//   RecIn (the second pass): keys_in holds records and vals_in the digit bytes; the key is formed in
+//     registers as digit << shift | low half, so the ranking and the starts run unchanged.
+// A record tile is staged once; the digit of a staged position comes from a byte per position kept in
+// the per-wave counters' LDS, dead by then (the next pass's digit bytes take a second, 4 KB round).
+// (The 128-digit kOutRecordsDigit instance spills 16 B/lane at its 64-VGPR budget; the 256-digit one in its
+// place measured the same: profiles/r09_tile_sort_records.md.)
 constexpr int kNarrowRadix = 128;
 constexpr long long kNarrowMaxN = 12ll << 20;
-template <typename K, bool Starts = false, int D = kRadix>
+constexpr int kOutPairs = 0, kOutRecords = 1, kOutRecordsDigit = 2;
+template <typename K, bool Starts = false, int D = kRadix, int Out = kOutPairs, bool RecIn = false>
 __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kRadix ? 1 : 8))) void radix_scatter_kernel(const K* __restrict__ keys_in,
                                                                 const uint32_t* __restrict__ vals_in,
                                                                 K* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
@@ -230,7 +261,8 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
                                                                 const uint32_t* __restrict__ tile_prefix,
                                                                 const uint32_t* __restrict__ totals,
                                                                 const uint32_t* __restrict__ totals0, int b0,
-                                                                uint32_t* __restrict__ starts)
+                                                                uint32_t* __restrict__ starts, int next_shift,
+                                                                uint32_t next_mask)
 {
     __shared__ __attribute__((aligned(16))) K s_stage[kTile];  // keys by tile-local rank, then values
     __shared__ uint32_t s_cnt[kSWaves][D];              // per-wave running counters
@@ -262,12 +294,38 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
     // the pass's input, dead after the pass, read with non-temporal loads so it does not displace the
     // output the next pass reads: scatter 42.8 -> 40.6 us (1080p D2 view), 4K sort 872 -> 834 us
     // (profiles/r04_scatter_nt.md)
+    // RecIn: the wave's kSItems * 64 digit bytes are contiguous: one 8-byte load per lane, handed round
+    // through the wave's part of the staging buffer (free until the ranks are known; LDS operations of
+    // one wave retire in order).  Byte loads, 64 B per instruction, share their lines between two rounds
+    // and measured 4.5 us slower per pass than the pairs they replace.
+    static_assert(!RecIn || kSItems == 8, "a lane's share of the wave's digit bytes is one 8-byte load");
+    uint8_t* s_in = reinterpret_cast<uint8_t*>(s_stage) + wave * (kSItems * kWave);
+    if (RecIn) {
+        const uint8_t* dg = reinterpret_cast<const uint8_t*>(vals_in);
+        const long long i8 = seg + lane * 8;
+        uint64_t d8 = 0ull;
+        if (i8 + 8 <= n && (reinterpret_cast<uintptr_t>(dg) & 7) == 0) {
+            d8 = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(dg + i8));
+        } else {
+            for (int b = 0; b < 8; b++)
+                if (i8 + b < n) d8 |= (uint64_t)dg[i8 + b] << (8 * b);
+        }
+        *reinterpret_cast<uint64_t*>(s_in + lane * 8) = d8;
+        __builtin_amdgcn_wave_barrier();
+    }
 #pragma unroll
     for (int r = 0; r < kSItems; r++) {
         const long long i = seg + r * kWave + lane;
         ok[r] = i < n;
-        k[r] = ok[r] ? __builtin_nontemporal_load(keys_in + i) : K(0);
-        v[r] = ok[r] ? __builtin_nontemporal_load(vals_in + i) : 0u;
+        if (RecIn) {
+            const uint64_t rec = ok[r] ? __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(keys_in) + i) : 0ull;
+            const uint32_t dg = s_in[r * kWave + lane];
+            k[r] = (K)(((uint64_t)dg << shift) | (uint32_t)rec);
+            v[r] = (uint32_t)(rec >> 32);
+        } else {
+            k[r] = ok[r] ? __builtin_nontemporal_load(keys_in + i) : K(0);
+            v[r] = ok[r] ? __builtin_nontemporal_load(vals_in + i) : 0u;
+        }
     }
     // the digits' global bases, scanned while the tile's loads are in flight (workgroup barriers
     // do not wait for global loads)
@@ -300,11 +358,52 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
         if (ok[r]) {
             const uint32_t dd = digit_of(k[r], shift, mask);
             pos[r] = s_start[dd] + s_cnt[wave][dd] + rank[r];
-            s_stage[pos[r]] = k[r];
+            if (Out == kOutPairs) s_stage[pos[r]] = k[r];
         }
     }
     __syncthreads();
     const int count = (int)((n - base) < kTile ? (n - base) : kTile);
+    if (Out != kOutPairs) {  // after the barrier: every counter is read, their LDS takes the positions' digits
+        static_assert(Out == kOutPairs || Starts == (Out == kOutRecords), "the last pass writes the final records");
+        static_assert(sizeof(s_cnt) >= kTile && D <= 256, "a digit byte per staged position");
+        uint8_t* s_digit = reinterpret_cast<uint8_t*>(&s_cnt[0][0]);
+#pragma unroll
+        for (int r = 0; r < kSItems; r++) {
+            if (ok[r]) {
+                s_stage[pos[r]] = (K)(((uint64_t)v[r] << 32) | (uint32_t)k[r]);
+                s_digit[pos[r]] = (uint8_t)digit_of(k[r], shift, mask);
+                // the next pass's digit rides above the position (< 4096): the keys die here
+                if (Out == kOutRecordsDigit) pos[r] |= digit_of(k[r], next_shift, next_mask) << 16;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kSItems; j++) {  // run-contiguous: position i = t + kSBlock j
+            const int i = t + j * kSBlock;
+            if (i < count) {
+                const uint32_t d = s_off[s_digit[i]] + i;
+                if (d < n) keys_out[d] = s_stage[i];  // always true for consistent counts
+            }
+        }
+        if (Out == kOutRecordsDigit) {
+            __syncthreads();  // every record read: the staging buffer takes the next pass's digits
+            uint8_t* s_next = reinterpret_cast<uint8_t*>(s_stage);
+            uint8_t* digits_out = reinterpret_cast<uint8_t*>(vals_out);
+#pragma unroll
+            for (int r = 0; r < kSItems; r++)
+                if (ok[r]) s_next[pos[r] & 0xffffu] = (uint8_t)(pos[r] >> 16);
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < kSItems; j++) {
+                const int i = t + j * kSBlock;
+                if (i < count) {  // (the destination again, not eight registers kept across the barriers)
+                    const uint32_t d = s_off[s_digit[i]] + i;
+                    if (d < n) digits_out[d] = s_next[i];
+                }
+            }
+        }
+        return;
+    }
     uint32_t dst[kSItems];
 #pragma unroll
     for (int j = 0; j < kSItems; j++) {  // keys, run-contiguous: position i = t + kSBlock j

@@ -28,6 +28,9 @@ union QueueLds {
 
 // The segment's pairs into registers, with the AND / OR / MIN / MAX of their low halves and hd, the
 // OR of (high half ^ ref_hi): nonzero when any pair's high half differs from the first pair's.
+// Packed: src_k holds {low key half, value} records (radix_scatter_kernel's Packed output) and every
+// high half is ref_hi, the segment id; src_v is not read.
+template <bool Packed = false>
 __device__ __forceinline__ void seg_load(const uint64_t* __restrict__ src_k, const uint32_t* __restrict__ src_v,
                                          const uint32_t begin, const uint32_t m, const uint32_t ref_hi,
                                          uint64_t (&k)[kSegItems], uint32_t (&v)[kSegItems], uint32_t& a, uint32_t& o,
@@ -38,14 +41,34 @@ __device__ __forceinline__ void seg_load(const uint64_t* __restrict__ src_k, con
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = t + q * kBlock;
         if (i < m) {
-            k[q] = src_k[begin + i];
-            v[q] = src_v[begin + i];
+            if (Packed) {
+                const uint2 rec = reinterpret_cast<const uint2*>(src_k)[begin + i];
+                k[q] = ((uint64_t)ref_hi << 32) | rec.x;
+                v[q] = rec.y;
+            } else {
+                k[q] = src_k[begin + i];
+                v[q] = src_v[begin + i];
+            }
             const uint32_t x = (uint32_t)k[q];
             a &= x;
             o |= x;
             lo = min(lo, x);
             hi = max(hi, x);
             hd |= (uint32_t)(k[q] >> 32) ^ ref_hi;
+        }
+    }
+}
+
+// The pairs seg_load<true> expanded, written back where they were read (each thread its own elements).
+__device__ __forceinline__ void store_loaded(const uint64_t (&k)[kSegItems], const uint32_t (&v)[kSegItems],
+                                             const uint32_t begin, const uint32_t m, uint64_t* dk, uint32_t* dv)
+{
+#pragma unroll
+    for (int q = 0; q < kSegItems; q++) {
+        const uint32_t i = threadIdx.x + q * kBlock;
+        if (i < m) {
+            dk[begin + i] = k[q];
+            dv[begin + i] = v[q];
         }
     }
 }
@@ -270,7 +293,7 @@ __device__ __forceinline__ void open_local(const uint64_t* keys, const BigQueue&
 #pragma unroll
         for (int u = 0; u < kChunk / kBlock; u++) {
             const uint32_t i = i0 + u * kBlock + t;
-            x[u] = (uint32_t)keys[begin + (i < m ? i : 0u)];  // a repeat changes no MIN / MAX
+            x[u] = key_low(keys, begin + (i < m ? i : 0u));  // a repeat changes no MIN / MAX
         }
 #pragma unroll
         for (int u = 0; u < kChunk / kBlock; u++) {
@@ -318,8 +341,40 @@ __device__ __forceinline__ void open_local(const uint64_t* keys, const BigQueue&
     emit_jobs(q, e);
 }
 
+// A segment of packed records (radix_scatter_kernel's Packed output) rewritten in place as whole pairs:
+// keys[i] = seg << 32 | low half, vals[i] = value.  Each thread rewrites the elements it read itself,
+// kExpandItems loads in flight.  The low halves keep their values and places, so whoever reads only
+// those meanwhile (a scout's open_local) sees no change.
+constexpr int kExpandItems = 8;
+__device__ __forceinline__ void expand_records(uint64_t* keys, uint32_t* vals, const uint32_t begin, const uint32_t m,
+                                               const uint32_t seg)
+{
+    const uint2* recs = reinterpret_cast<const uint2*>(keys);
+    const uint64_t khi = (uint64_t)seg << 32;
+    for (uint32_t i0 = 0; i0 < m; i0 += kExpandItems * kBlock) {
+        uint2 rec[kExpandItems];
+#pragma unroll
+        for (int u = 0; u < kExpandItems; u++) {
+            const uint32_t i = i0 + u * kBlock + threadIdx.x;
+            rec[u] = i < m ? recs[begin + i] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < kExpandItems; u++) {
+            const uint32_t i = i0 + u * kBlock + threadIdx.x;
+            if (i < m) {
+                keys[begin + i] = khi | rec[u].x;
+                vals[begin + i] = rec[u].y;
+            }
+        }
+    }
+}
+
 // Workgroup b sorts segment b in place by the low 32 key bits (sort_segment); a segment of more
 // than kSegCap pairs becomes a record of the partition queue (big_segment_kernel runs it).
+// Packed: `keys` arrives as packed records and segment b's high key half is b.  Every way out leaves
+// whole keys and values behind; a segment that this kernel does not sort itself is expanded in place
+// by its own workgroup first, so the queue's kernels and the one-workgroup forms see ordinary pairs.
+template <bool Packed>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kSegWaves))) void segment_sort_kernel(
     uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, const uint32_t* __restrict__ starts,
     uint2* __restrict__ ranges_out, const int nseg, const BigQueue q)
@@ -382,8 +437,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kSegWave
     const uint2 r = make_uint2(starts[seg], starts[seg + 1]);
     if (ranges_out && threadIdx.x == 0) ranges_out[seg] = r.y > r.x ? r : make_uint2(0u, 0u);
     const uint32_t begin = r.x, m = r.y - r.x;
-    if (r.y <= r.x + 1) return;  // absent or single pair: already in place
+    if (r.y <= r.x + 1) {  // absent or single pair: already in place
+        if (Packed && r.y == r.x + 1) expand_records(keys, vals, begin, 1u, seg);
+        return;
+    }
     if (m > (uint32_t)kSegCap) {
+        if (Packed) {
+            // (a scout may be reading the segment's low key halves meanwhile: they do not change)
+            expand_records(keys, vals, begin, m, seg);
+            if (m <= (uint32_t)kQueueMin || kScouts == 0) __syncthreads();  // this workgroup reads the pairs next
+        }
         if (m <= (uint32_t)kQueueMin) {  // mildly hot: this workgroup, overlapped with the others
             segment_sort_global(keys, vals, q.alt_k, q.alt_v, begin, m, lds.big);
             return;
@@ -410,19 +473,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kSegWave
     uint32_t a = 0xffffffffu, o = 0, lo = 0xffffffffu, hi = 0;
     // the segment's first high key half: the segment id (tile), and with no bits above end_bit -- as
     // hidegs_sort_tile_pairs' callers guarantee -- every pair's high half; `hd` records any that differs
-    const uint32_t ref_hi = (uint32_t)(keys[begin] >> 32);
+    // (Packed: the segment id itself, with no load to wait for)
+    const uint32_t ref_hi = Packed ? seg : (uint32_t)(keys[begin] >> 32);
     uint32_t hd = 0;
-    seg_load(keys, vals, begin, m, ref_hi, k, v, a, o, lo, hi, hd);
+    seg_load<Packed>(keys, vals, begin, m, ref_hi, k, v, a, o, lo, hi, hd);
     BucketShared& sh = lds.bucket;
     for (int i = t; i < kBuckets; i += kBlock) sh.fill[i] = 0u;
     const SegStats st = segment_stats(a, o, lo, hi, s_and, s_or);
     const uint32_t diff = st.diff;  // low key bits that vary over the segment
-    if (diff == 0) return;  // equal low keys: the input order is the stable order
+    if (diff == 0) {  // equal low keys: the input order is the stable order
+        // (read again, not stored from k and v: keeping those live to here costs 28 B/lane of scratch)
+        if (Packed) expand_records(keys, vals, begin, m, seg);
+        return;
+    }
     const int shift = st.shift;
     uint32_t mixed_hi;
     const uint32_t fullest = bucket_starts(k, m, st.lo, shift, hd, sh, s_and, s_max, mixed_hi);
     if (fullest > (uint32_t)kMaxBucket || shift + kIndexBits > 32) {  // crowded depths, or fields too
-        // wide for 32 bits: the LSD form (block-uniform branch)
+        // wide for 32 bits: the LSD form (block-uniform branch), which reads whole pairs
+        if (Packed) store_loaded(k, v, begin, m, keys, vals);
         __syncthreads();
         segment_sort_lsd<true>(keys, vals, nullptr, nullptr, begin, m, diff, lds.lsd);
         return;
@@ -455,7 +524,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kSegWave
         }
     }
     __syncthreads();
-    if (!mixed_hi) {
+    if (Packed || !mixed_hi) {  // (Packed: one high half by construction)
         stage_compact(k, v, pos, begin, m, ref_hi, sh, keys, vals);
         return;
     }

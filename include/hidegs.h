@@ -184,6 +184,8 @@ int hidegs_identify_tile_ranges(const uint64_t* sorted_keys, long long n, uint32
  * followed by hidegs_identify_tile_ranges.  Keys are (tile << 32) | depth bits with tile < num_tiles.
  * The sort partitions the pairs by tile anyway; the partition's ranges are the output, so the
  * separate range pass is saved.  scratch: hidegs_sort_pairs_u64_scratch_bytes(n).
+ * A key with tile >= num_tiles breaks the contract: its pair is not sorted, and keys_out and vals_out
+ * are unspecified at the positions of such pairs (the call still writes inside its buffers only).
  */
 int hidegs_sort_tile_pairs(void* scratch, size_t scratch_bytes, const uint64_t* keys_in, uint64_t* keys_out,
                            const uint32_t* vals_in, uint32_t* vals_out, long long n, int num_tiles, uint32_t* ranges,

@@ -5,6 +5,9 @@ the checker or the timed CPU baseline.  The product packages (diff_gaussian_rast
 simple_knn, hidegs_amd) never import it.
 
   knn_mean3 / knn_mean3_subset  -- distCUDA2's value from its definition (knn_ref.c)
+  knn_mean3_grid                -- the same value on every point, bit for bit, found with uniform cell
+                                   grids instead of brute force (knn_grid_ref.c): finite input only,
+                                   fast enough for every point of a cloud of a million
   masked_adam                   -- one OurAdam step on one parameter tensor (adam_ref.c)
   stable_sort_pairs / inclusive_scan_u32 / tile_ranges -- generic integer restatements
      of the binning primitives (numpy), see binning.py
@@ -39,6 +42,8 @@ def lib() -> C.CDLL:
         dll.oracle_knn_mean3.restype = None
         dll.oracle_knn_mean3_subset.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]
         dll.oracle_knn_mean3_subset.restype = None
+        dll.oracle_knn_mean3_grid.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
+        dll.oracle_knn_mean3_grid.restype = C.c_int
         dll.oracle_masked_adam.argtypes = [C.c_void_p] * 5 + [C.c_longlong, C.c_int] + [C.c_double] * 5 + \
             [C.c_longlong]
         dll.oracle_masked_adam.restype = None
@@ -58,6 +63,20 @@ def knn_mean3(points: np.ndarray) -> np.ndarray:
     out = np.empty(pts.shape[0], dtype=np.float32)
     if pts.shape[0]:
         lib().oracle_knn_mean3(pts.ctypes.data, pts.shape[0], out.ctypes.data)
+    return out
+
+
+def knn_mean3_grid(points: np.ndarray) -> np.ndarray:
+    """knn_mean3's value for every point, bit for bit, by a cell-grid search (exact; see knn_grid_ref.c).
+    Raises ValueError on a non-finite coordinate: those inputs stay with knn_mean3."""
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    out = np.empty(pts.shape[0], dtype=np.float32)
+    if pts.shape[0]:
+        rc = lib().oracle_knn_mean3_grid(pts.ctypes.data, pts.shape[0], out.ctypes.data)
+        if rc == 1:
+            raise ValueError("knn_mean3_grid: non-finite coordinate (use knn_mean3)")
+        if rc != 0:
+            raise MemoryError("oracle_knn_mean3_grid: allocation failed")
     return out
 
 

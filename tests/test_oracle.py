@@ -64,6 +64,114 @@ def test_knn_oracle_subset_agrees(oracle_lib):
     assert np.array_equal(oracle_lib.knn_mean3_subset(pts, idx), full[idx])
 
 
+# ---- the grid oracle against the brute-force oracle ---------------------------------------------
+# knn_mean3_grid (knn_grid_ref.c) is what the every-point GPU tests above 100k points trust, so here it
+# must equal knn_mean3 on every point, as bit patterns, on each kind of cloud those tests use and on
+# the sets where a cell search goes wrong: far outliers, a core inside a shell, zero extent on an
+# axis, every point in one cell, mass ties, fewer than four points, distances that overflow or underflow.
+
+def grid_cloud(name):
+    import knn_clouds as kc
+    uniform = np.random.default_rng(1).random((30_000, 3), dtype=np.float32)
+    if name == "uniform":
+        return uniform
+    if name == "uniform_outliers":
+        return kc.with_outliers(uniform)
+    if name == "frustum":
+        return kc.frustum_points(40_000)
+    if name == "frustum_outliers":
+        return kc.with_outliers(kc.frustum_points(40_000))
+    if name == "sfm_like":
+        return kc.sfm_like(60_000)
+    if name == "sfm_like_no_outliers":
+        return kc.sfm_like(60_000, outliers=False)
+    if name == "core_shell":
+        return kc.core_shell(28_000, 12_000)
+    if name == "offset_cube":
+        return kc.offset_cube()
+    if name.startswith("P="):
+        return np.random.default_rng(int(name[2:])).random((int(name[2:]), 3), dtype=np.float32)
+    if name.startswith("scale_2^"):
+        return kc.range_scaled(int(name[len("scale_2^"):]))
+    return kc.degenerate(name)
+
+
+GRID_CLOUDS = ["uniform", "uniform_outliers", "frustum", "frustum_outliers", "sfm_like", "sfm_like_no_outliers",
+               "core_shell", "duplicates", "identical", "line", "plane", "ties_grid", "two_far_clusters",
+               "P=1", "P=2", "P=3", "P=4", "scale_2^66", "scale_2^68", "scale_2^-60", "scale_2^-66", "scale_2^-70",
+               "offset_cube"]
+
+
+@pytest.mark.parametrize("name", GRID_CLOUDS)
+def test_knn_grid_oracle_equals_brute_force_on_every_point(oracle_lib, name):
+    pts = grid_cloud(name)
+    got, exp = oracle_lib.knn_mean3_grid(pts), oracle_lib.knn_mean3(pts)
+    bad = np.flatnonzero(got.view(np.uint32) != exp.view(np.uint32))
+    assert bad.size == 0, f"{name}: {bad.size} mismatches, first {bad[:5]}: grid {got[bad[:5]]} brute {exp[bad[:5]]}"
+
+
+def test_knn_grid_oracle_equals_brute_force_on_random_mixtures(oracle_lib):
+    """300 seeded clouds of 1 to 4,000 points: one to five blobs whose sizes and distances span six
+    decades each, some flattened to a plane or a line, some snapped to a lattice (ties, duplicates).
+    They move the nested boxes, the cell size and the ring where the search stops through cases the
+    named clouds do not reach; every point is compared."""
+    g = np.random.default_rng(2024)
+    for case in range(300):
+        P = int(np.exp(g.uniform(0, np.log(4000))))
+        parts = []
+        left = P
+        for b in range(int(g.integers(1, 6))):
+            n = left if b == 4 else int(g.integers(0, left + 1))
+            blob = g.normal(0, 10.0 ** g.uniform(-3, 3), (n, 3)) * (g.random(3) < 0.8)
+            parts.append(blob + g.normal(0, 10.0 ** g.uniform(-3, 3), 3))
+            left -= n
+        parts.append(g.uniform(-1, 1, (left, 3)))
+        pts = np.concatenate(parts)
+        if g.random() < 0.3:
+            step = 10.0 ** g.uniform(-3, 1)
+            pts = np.round(pts / step) * step
+        pts = pts.astype(np.float32)
+        got, exp = oracle_lib.knn_mean3_grid(pts), oracle_lib.knn_mean3(pts)
+        bad = np.flatnonzero(got.view(np.uint32) != exp.view(np.uint32))
+        assert bad.size == 0, f"case {case} (P={P}): {bad.size} mismatches, first {bad[:5]}"
+
+
+def test_knn_grid_oracle_sfm_outliers_removed_only_where_they_were():
+    import knn_clouds as kc
+    a, b = kc.sfm_like(60_000), kc.sfm_like(60_000, outliers=False)
+    moved = np.flatnonzero((a != b).any(1))
+    assert 0 < moved.size <= 60_000 // 500 and np.abs(b).max() < 60 and np.abs(a).max() > 1000
+
+
+def test_knn_grid_oracle_independent_of_threads(oracle_lib):
+    pts = grid_cloud("sfm_like")
+    before = oracle_lib.set_threads(0)
+    outs = []
+    for th in (1, 3, 8):
+        assert oracle_lib.set_threads(th) == th
+        outs.append(oracle_lib.knn_mean3_grid(pts))
+    oracle_lib.set_threads(before)
+    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
+    assert np.array_equal(outs[0].view(np.uint32), outs[2].view(np.uint32))
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+def test_knn_grid_oracle_rejects_non_finite_input(oracle_lib, bad):
+    pts = np.random.default_rng(4).random((1000, 3), dtype=np.float32)
+    pts[617, 1] = bad
+    with pytest.raises(ValueError):
+        oracle_lib.knn_mean3_grid(pts)
+    assert oracle_lib.knn_mean3_grid(np.zeros((0, 3), np.float32)).shape == (0,)
+
+
+@pytest.mark.parametrize("log2_scale", [66, 68, -60, -66, -70])
+def test_range_scaled_clouds_hit_their_range(oracle_lib, log2_scale):
+    """The classes (inf, zero, denormal, normal) of the brute-force results on the range-scaled clouds:
+    the inputs of the GPU range tests cannot drift out of the range they are meant to hit."""
+    import knn_clouds as kc
+    assert kc.result_classes(oracle_lib.knn_mean3(kc.range_scaled(log2_scale))) == kc.RANGE_CLASSES[log2_scale]
+
+
 # ---- binning oracles ---------------------------------------------------------------
 
 @pytest.mark.parametrize("n,bits", [(64, 7), (8160, 13), (32400, 15), (0, 1), (1, 1), (2, 2), (255, 8), (256, 9),

@@ -29,6 +29,8 @@ SETS = {
     "plane2M": lambda: torch.cat([torch.rand(2_000_000, 2), torch.zeros(2_000_000, 1)], 1),
     # the input of tests/test_knn_gpu.py::test_bail_out_wave_every_point
     "core_shell40k": lambda: torch.from_numpy(core_shell(np.random.default_rng(7), 28_000, 12_000)),
+    # the input of tests/test_knn_every_point_gpu.py::test_core_shell_700k_every_point
+    "core_shell700k": lambda: torch.from_numpy(core_shell(np.random.default_rng(7), 490_000, 210_000)),
 }
 for name in sys.argv[1:] or SETS:
     print(name, flush=True)

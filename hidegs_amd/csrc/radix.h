@@ -19,10 +19,43 @@ __device__ __forceinline__ uint32_t digit_of(K key, int shift, uint32_t mask)
 // digit group bumps the counter (LDS ops of one wave retire in order, so the read precedes
 // the write).
 // With Based, the digit is taken of (low key half - dbase) instead (the partition queue's digits).
-template <typename K, int R, bool Based = false>
+// With LaneMask, the lanes sharing a digit are found through LDS instead of by ballots: lane_mask =
+// one 64-bit word per digit for this wave, zero on entry and again on exit.  Every valid lane ORs its
+// lane bit into its digit's word and reads the word back: an OR has no order, so the word does not
+// depend on the order in which the LDS serves the lanes of one atomic instruction, and the rank among
+// the lanes below is the same mbcnt as in the ballot form.  The lowest lane of the group clears the
+// word behind the read.  One atomic and one 8-byte read per round in place of ~7 VALU instructions
+// per varying digit bit; `vary` is unused.
+template <typename K, int R, bool Based = false, bool LaneMask = false>
 __device__ __forceinline__ void wave_rank(const K (&k)[R], const bool (&ok)[R], int shift, uint32_t mask,
-                                          uint32_t* cnt, uint32_t (&rank)[R], uint32_t vary, uint32_t dbase = 0u)
+                                          uint32_t* cnt, uint32_t (&rank)[R], uint32_t vary, uint32_t dbase = 0u,
+                                          uint64_t* lane_mask = nullptr)
 {
+    if (LaneMask) {
+        const uint64_t bit = 1ull << lane_id();
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t d = Based ? ((((uint32_t)k[r]) - dbase) >> shift) & mask : digit_of(k[r], shift, mask);
+            if (ok[r]) __hip_atomic_fetch_or(&lane_mask[d], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __builtin_amdgcn_wave_barrier();
+            uint64_t same = 0ull;  // lanes with the same digit
+            uint32_t old = 0;
+            if (ok[r]) {
+                old = cnt[d];
+                same = lane_mask[d];
+            }
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t below =
+                __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
+            if (ok[r] && below == 0) {
+                cnt[d] = old + (uint32_t)__popcll(same);
+                lane_mask[d] = 0ull;
+            }
+            __builtin_amdgcn_wave_barrier();
+            rank[r] = old + below;
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const uint32_t d = Based ? ((((uint32_t)k[r]) - dbase) >> shift) & mask : digit_of(k[r], shift, mask);
@@ -273,7 +306,9 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
 
     const int t = threadIdx.x;
     const int lane = lane_id();
-    const int wave = t / kWave;
+    // wave-uniform, and told so: the wave's LDS bases (counters, lane masks) and its items' offset stay in
+    // scalar registers, which the 64-VGPR instances have none to spare for
+    const int wave = __builtin_amdgcn_readfirstlane(t / kWave);
     const bool digit_thread = t < D;  // thread d owns digit d in the digit scans
     for (int i = t; i < kSWaves * D; i += kSBlock) (&s_cnt[0][0])[i] = 0;
     // neighbouring tiles on one XCD: 46.3 -> 42.9 us per pass at 8M pairs (their shared output lines at
@@ -299,7 +334,8 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
     // one wave retire in order).  Byte loads, 64 B per instruction, share their lines between two rounds
     // and measured 4.5 us slower per pass than the pairs they replace.
     static_assert(!RecIn || kSItems == 8, "a lane's share of the wave's digit bytes is one 8-byte load");
-    uint8_t* s_in = reinterpret_cast<uint8_t*>(s_stage) + wave * (kSItems * kWave);
+    uint8_t* s_part = reinterpret_cast<uint8_t*>(s_stage) + wave * (sizeof(K) * kTile / kSWaves);  // the wave's own part
+    uint8_t* s_in = s_part;
     if (RecIn) {
         const uint8_t* dg = reinterpret_cast<const uint8_t*>(vals_in);
         const long long i8 = seg + lane * 8;
@@ -333,8 +369,17 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
     const uint32_t digit_base = block_exclusive_scan<kSWaves>(digit_total, s_wave, &dummy) + digit_prefix;
     // (at the end of the kernel instead, with the keys kept live: 73 VGPRs against 61, same time)
     if (Starts) segment_starts<K, kSItems, D>(k, ok, shift, mask, n, tile, ntiles, base, digit_base, low_base, b0, starts);
+    // the ranking's lane masks (wave_rank's LaneMask form), D words of 8 bytes, live in the wave's own
+    // part of the staging buffer as well: s_in's bytes are in k[] by now (LDS operations of one wave
+    // retire in order), and the barrier after the ranking separates the masks from the staged keys
+    static_assert(D * sizeof(uint64_t) <= sizeof(K) * kTile / kSWaves && D % kWave == 0, "the masks fit the wave's part");
+    uint64_t* s_mask = reinterpret_cast<uint64_t*>(s_part);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < D / kWave; j++) s_mask[j * kWave + lane] = 0ull;
+    __builtin_amdgcn_wave_barrier();
     uint32_t rank[kSItems];
-    wave_rank<K, kSItems>(k, ok, shift, mask, s_cnt[wave], rank, mask);
+    wave_rank<K, kSItems, false, true>(k, ok, shift, mask, s_cnt[wave], rank, mask, 0u, s_mask);
     __syncthreads();
 
     uint32_t tile_count_d = 0;  // thread d: count of digit d in waves before each wave, in place

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/hidegs.h and include/hidegs_rows.h (hidegs_amd/libhidegs.so).
+"""ctypes binding of the C ABI in include/hidegs.h, include/hidegs_rows.h and include/hidegs_resize.h
+(hidegs_amd/libhidegs.so).
 
 This is the only place that loads the native library.  It fails loudly: a missing
 library raises ImportError-like RuntimeError at first use, and a non-zero return
@@ -95,18 +96,30 @@ ROW_SIGNATURES = {
     "hidegs_scatter_rows": (I, [P, I, P, LL, P]),
 }
 
+
+class ResizeField(C.Structure):
+    """hidegs_resize_field (include/hidegs_resize.h)."""
+    _fields_ = [("src", C.c_void_p), ("append", C.c_void_p), ("dst", C.c_void_p), ("n_rows", C.c_longlong),
+                ("width", C.c_int)]
+
+
+# include/hidegs_resize.h
+RESIZE_SIGNATURES = {
+    "hidegs_resize_rows": (I, [P, I, P, LL, LL, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
 
 def load_library(path: str) -> C.CDLL:
-    """A build of the ABI at `path` with every signature of include/hidegs.h and include/hidegs_rows.h
+    """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h and hidegs_resize.h
     bound (lib() for the product build; tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
                            "(or __graft_entry__.build()) to compile it for gfx950")
     dll = C.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

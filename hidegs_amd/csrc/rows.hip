@@ -17,6 +17,10 @@
 // ascending indices, ascending across rows.  A thread owns kUnroll units a workgroup-stride apart and
 // steps (packed row, column) from one to the next with host-computed increments: one division per
 // thread, not per element.
+//
+// Resize (include/hidegs_resize.h): the row surgery of densification -- prune by a keep list, append new
+// rows -- on every per-Gaussian tensor in one launch per kMaxFields.  The same unit stepping over the dense
+// destination, which is written from three sources: kept rows gathered, appended rows copied, or zeros.
 #include <stdint.h>
 
 #include <string>
@@ -258,6 +262,176 @@ int move_rows(bool scatter, const hidegs_row_field* fields, int nfields, const u
     return check_launch(name, stream, 0);
 }
 
+// ============================== resize =========================================
+// One field of a resize: dst = [src rows named by keep | append rows or zeros], dense.
+struct ResizeField {
+    const uint32_t* src;
+    const uint32_t* append;  // NULL: the appended rows are zeros
+    const uint32_t* safe;    // one readable unit for the lanes that write zeros (src or append); NULL: all zeros
+    uint32_t* dst;
+    long long n_rows;
+    long long kept;    // k * width / unit: the units gathered from src
+    long long units;   // (k + n_append) * width / unit
+    uint32_t width;
+    uint32_t unit;     // floats per access: 4 (16-byte accesses on all three sides) or 1
+    uint32_t step_j;   // as RowField's
+    uint32_t step_c;
+    double inv_w;
+};
+
+// Workgroups [first[f], first[f + 1]) own field f.
+struct ResizeBatch {
+    int count;
+    int first[kMaxFields + 1];
+    ResizeField f[kMaxFields];
+};
+
+// Consecutive lanes take consecutive units of dst.  A unit below F.kept is gathered (dst row j from src row
+// keep[j], or row j itself without a keep array; zeros if that row is past the source); one at or after it
+// comes from append at unit - F.kept, or is zeros.  Which of the two is workgroup-uniform except in the one
+// workgroup that holds unit F.kept.
+template <typename V, bool kKeep>
+__device__ __forceinline__ void resize_units(const ResizeField& F, long long u0, const uint32_t* __restrict__ keep)
+{
+    constexpr uint32_t kUnit = sizeof(V) / sizeof(uint32_t);
+    const long long e0 = u0 * kUnit;  // the workgroup's first dst element
+    const long long j0 = row_of(e0, F.width, F.inv_w);
+    const uint32_t r = (uint32_t)(e0 - j0 * (long long)F.width) + threadIdx.x * kUnit;  // < width + 1024
+    const uint32_t q = r / F.width;
+    long long j = j0 + q;            // dst row and column of this thread's first unit
+    uint32_t c = r - q * F.width;
+    uint32_t idx[kUnroll], col[kUnroll];
+#pragma unroll
+    for (int i = 0; i < kUnroll; i++) {  // every index load issued before any is used
+        const long long u = u0 + i * kBlock + threadIdx.x;
+        // a gathered unit (u < F.kept) has j < k; entry 0 exists (keep is passed only where k >= 1)
+        idx[i] = kKeep ? keep[u < F.kept ? j : 0] : (uint32_t)j;
+        col[i] = c;
+        c += F.step_c;
+        j += F.step_j;
+        if (c >= F.width) {
+            c -= F.width;
+            j++;
+        }
+    }
+    const V* from[kUnroll];          // where the unit is read: F.safe where it is zeros, so the loads need no branch
+    bool zero[kUnroll];
+#pragma unroll
+    for (int i = 0; i < kUnroll; i++) {
+        const long long u = u0 + i * kBlock + threadIdx.x;
+        const bool in_src = (u < F.kept) & ((long long)idx[i] < F.n_rows);  // an index past the rows is never dereferenced
+        const bool in_append = (u >= F.kept) & (u < F.units) & (F.append != nullptr);
+        const uint32_t* base = in_src ? F.src : (in_append ? F.append : F.safe);
+        const size_t at = in_src ? ((size_t)idx[i] * F.width + col[i]) / kUnit : (in_append ? (size_t)(u - F.kept) : 0);
+        from[i] = reinterpret_cast<const V*>(base) + at;
+        zero[i] = !(in_src | in_append);
+    }
+    V v[kUnroll];
+#pragma unroll
+    for (int i = 0; i < kUnroll; i++) v[i] = *from[i];  // every load issued before the first store
+    V* dst = reinterpret_cast<V*>(F.dst);
+#pragma unroll
+    for (int i = 0; i < kUnroll; i++) {
+        const long long u = u0 + i * kBlock + threadIdx.x;
+        if (u < F.units) dst[u] = zero[i] ? V{} : v[i];
+    }
+}
+
+// A field with nothing to read (no source row and no appended rows given): zeros.
+template <typename V>
+__device__ __forceinline__ void zero_units(const ResizeField& F, long long u0)
+{
+    V* dst = reinterpret_cast<V*>(F.dst);
+#pragma unroll
+    for (int i = 0; i < kUnroll; i++) {
+        const long long u = u0 + i * kBlock + threadIdx.x;
+        if (u < F.units) dst[u] = V{};
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void resize_rows_kernel(const ResizeBatch batch, const uint32_t* __restrict__ keep)
+{
+    // workgroup-uniform selects over constant indices: the descriptors stay in scalar registers
+    ResizeField F = batch.f[0];
+    int first = batch.first[0];
+#pragma unroll
+    for (int i = 1; i < kMaxFields; i++) {
+        if (i < batch.count && (int)blockIdx.x >= batch.first[i]) {
+            F = batch.f[i];
+            first = batch.first[i];
+        }
+    }
+    const long long u0 = (long long)((int)blockIdx.x - first) * kUnitsPerBlock;
+    if (!F.safe) {
+        if (F.unit == 4)
+            zero_units<u32x4>(F, u0);
+        else
+            zero_units<uint32_t>(F, u0);
+    } else if (keep) {
+        if (F.unit == 4)
+            resize_units<u32x4, true>(F, u0, keep);
+        else
+            resize_units<uint32_t, true>(F, u0, keep);
+    } else {
+        if (F.unit == 4)
+            resize_units<u32x4, false>(F, u0, keep);
+        else
+            resize_units<uint32_t, false>(F, u0, keep);
+    }
+}
+
+int resize_rows(const hidegs_resize_field* fields, int nfields, const uint32_t* keep, long long k, long long n_append,
+                hipStream_t stream)
+{
+    const std::string who = "resize_rows";
+    if (nfields < 0) return fail(HIDEGS_E_ARG, who + ": negative field count");
+    if (k < 0 || n_append < 0 || k > kSelectMax || n_append > kSelectMax || k + n_append > kSelectMax)
+        return fail(HIDEGS_E_ARG, who + ": k, n_append and k + n_append must be in [0, 2^31)");
+    if (nfields > 0 && !fields) return fail(HIDEGS_E_ARG, who + ": NULL field list");
+    for (int i = 0; i < nfields; i++) {
+        if (fields[i].width < 1) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": width < 1");
+        if (fields[i].n_rows < 0) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": negative n_rows");
+    }
+    if (k + n_append == 0 || nfields == 0) return 0;
+    for (int i = 0; i < nfields; i++) {
+        if (!fields[i].dst || (k > 0 && fields[i].n_rows > 0 && !fields[i].src))
+            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": NULL pointer");
+        if (!keep && k > fields[i].n_rows)
+            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": without keep, k must not exceed n_rows");
+    }
+    if (k == 0) keep = nullptr;  // no row is gathered: the kernel reads no entry
+    for (int i0 = 0; i0 < nfields; i0 += kMaxFields) {  // kMaxFields per launch
+        ResizeBatch batch;
+        batch.count = 0;
+        long long blocks = 0;
+        for (int i = i0; i < nfields && i < i0 + kMaxFields; i++) {
+            const hidegs_resize_field& a = fields[i];
+            ResizeField F;
+            F.src = reinterpret_cast<const uint32_t*>(k > 0 && a.n_rows > 0 ? a.src : nullptr);
+            F.append = reinterpret_cast<const uint32_t*>(n_append > 0 ? a.append : nullptr);
+            F.safe = F.src ? F.src : F.append;
+            F.dst = reinterpret_cast<uint32_t*>(a.dst);
+            F.n_rows = a.n_rows;
+            F.width = (uint32_t)a.width;
+            // width a multiple of 4 and every base on 16 bytes: every row start and every quad is aligned, and
+            // k * width is a multiple of 4, so no quad holds both gathered and appended floats
+            F.unit = (a.width % 4 == 0 && aligned16(F.src) && aligned16(F.append) && aligned16(a.dst)) ? 4u : 1u;
+            F.kept = k * (long long)a.width / F.unit;
+            F.units = (k + n_append) * (long long)a.width / F.unit;
+            F.step_j = (uint32_t)(kBlock * F.unit) / F.width;
+            F.step_c = (uint32_t)(kBlock * F.unit) % F.width;
+            F.inv_w = 1.0 / (double)a.width;
+            batch.first[batch.count] = (int)blocks;
+            batch.f[batch.count++] = F;
+            blocks += (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
+            if (blocks > 0x7fffffffLL) return fail(HIDEGS_E_ARG, who + ": fields too large for one launch");
+        }
+        batch.first[batch.count] = (int)blocks;
+        HIDEGS_LAUNCH("resize_rows", resize_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch, keep);
+    }
+    return check_launch("resize_rows", stream, 0);
+}
+
 }  // namespace
 }  // namespace hidegs
 
@@ -301,4 +475,11 @@ extern "C" int hidegs_scatter_rows(const hidegs_row_field* fields, int nfields, 
 {
     if (int rc = hidegs::take_async_error("hidegs_scatter_rows", hidegs::as_stream(stream))) return rc;
     return hidegs::move_rows(true, fields, nfields, indices, k, hidegs::as_stream(stream));
+}
+
+extern "C" int hidegs_resize_rows(const hidegs_resize_field* fields, int nfields, const uint32_t* keep, long long k,
+                                  long long n_append, void* stream)
+{
+    if (int rc = hidegs::take_async_error("hidegs_resize_rows", hidegs::as_stream(stream))) return rc;
+    return hidegs::resize_rows(fields, nfields, keep, k, n_append, hidegs::as_stream(stream));
 }

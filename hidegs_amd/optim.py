@@ -17,6 +17,10 @@ parameter's update (an `AdamStepPlan`) without running it; the plan then runs wh
 by row range.  The view-DP exchange uses the row ranges to update each gradient bucket as soon as
 its all-reduce has landed (hidegs_amd.view_dp.ViewDPExchange.exchange_and_step).
 
+`resize_rows(keep, append, extra)` follows densification: parameters, moments and per-row companions are
+pruned and extended by one launch per 8 tensors (hidegs_amd.resize, csrc/rows.hip), and the parameters and
+`state` are swapped consistently, instead of a boolean index and a cat per tensor on `optimizer.state`.
+
 Not supported, as in the reference's masked path, which fails on them with a shape error:
 amsgrad, maximize; capturable (a different op sequence) is not reproduced.
 """
@@ -158,6 +162,78 @@ class Adam(Optimizer):
                     float(group["eps"]), float(group["weight_decay"]), step)
                 plan._add(p, dev, desc, (p, p.grad, state["exp_avg"], state["exp_avg_sq"], mask))
         return plan
+
+    def _named_params(self, what: str):
+        """[(group name, group, its one parameter)]: groups as HiDeGS builds them, or ValueError naming the group."""
+        out, seen = [], set()
+        for i, group in enumerate(self.param_groups):
+            name = group.get("name")
+            if name is None:
+                raise ValueError(f"{what}: parameter group {i} has no \"name\"")
+            if len(group["params"]) != 1:
+                raise ValueError(f"{what}: group {name!r} holds {len(group['params'])} parameters, expected one")
+            if name in seen:
+                raise ValueError(f"{what}: two groups are named {name!r}")
+            seen.add(name)
+            out.append((name, group, group["params"][0]))
+        return out
+
+    @torch.no_grad()
+    def resize_rows(self, keep=None, append=None, extra=None):
+        """Prune and append Gaussians: every group's parameter, its moments and the per-row companions in
+        `extra` are resized alike by one `hidegs_amd.resize.resize_rows` call (one host synchronisation).
+
+        keep    1-D bool / uint8 device mask over the rows (non-zero: the row stays), or None to keep all.
+        append  {group name: new rows}, naming every group (or none): the rows appended to each parameter.
+        extra   {name: tensor} with one row per Gaussian (the densification statistics): resized by the same
+                `keep`, their appended rows zero.
+        Every group's parameter is replaced by a new nn.Parameter (requires_grad, no .grad) and `self.state` is
+        re-keyed to it: exp_avg and exp_avg_sq keep the kept rows and are zero on the appended ones, "step"
+        and the group's hyper-parameters are unchanged, a parameter without state gets none.  Bit for bit
+        torch.cat((p[keep], new)) for parameters and torch.cat((m[keep], zeros_like(new))) for moments and
+        extras.  Returns (params_by_name, extra_by_name).  A gradient arena has to follow:
+        `arena.resized(n_new).reattach(params)` (hidegs_amd.view_dp.GradArena).
+        """
+        from hidegs_amd.resize import resize_rows
+
+        named = self._named_params("resize_rows")
+        append = dict(append or {})
+        extra = dict(extra or {})
+        names = [name for name, _, _ in named]
+        for name in append:
+            if name not in names:
+                raise ValueError(f"resize_rows: append names an unknown group {name!r} (groups: {names})")
+        if append:
+            for name in names:
+                if name not in append:
+                    raise ValueError(f"resize_rows: append has no rows for group {name!r}")
+        n_append = None if append else 0  # the appended rows give the count
+        tensors, new_rows, slots = [], [], []
+        for name, _, p in named:
+            tensors.append(p.detach())
+            new_rows.append(append.get(name))
+            slots.append(("param", name))
+            state = self.state.get(p)
+            if state:  # lazy initialisation stays: no state, none made
+                for key in ("exp_avg", "exp_avg_sq"):
+                    tensors.append(state[key])
+                    new_rows.append(None)
+                    slots.append((key, name))
+        for name, t in extra.items():
+            tensors.append(t)
+            new_rows.append(None)
+            slots.append(("extra", name))
+        outs = dict(zip(slots, resize_rows(tensors, keep, new_rows, n_append)))
+        params, extras = {}, {name: outs[("extra", name)] for name in extra}
+        for name, group, old in named:
+            new = torch.nn.Parameter(outs[("param", name)], requires_grad=True)
+            group["params"] = [new]
+            state = self.state.pop(old, None)
+            if state:
+                state["exp_avg"], state["exp_avg_sq"] = outs[("exp_avg", name)], outs[("exp_avg_sq", name)]
+                self.state[new] = state
+            params[name] = new
+        return params, extras
 
     @torch.no_grad()
     def step(self, relevant, closure=None):

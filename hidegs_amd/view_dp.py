@@ -121,7 +121,10 @@ class GradArena:
     (the 3DGS default), re-creating the parameters (densification) or assigning `.grad` detaches
     it, and autograd then writes a fresh tensor the arena never sees.  Call `zero_()` instead of
     zero_grad, and `attach` again after the parameters change; the exchange checks the link
-    (`check_attached`) and raises when it is broken.
+    (`check_attached`) and raises when it is broken.  After a change of the row count
+    (`hidegs_amd.optim.Adam.resize_rows`) the arena has to follow it: `arena = arena.resized(n_new)` is a
+    new zeroed arena of the same fields, and `arena.reattach(params)` links the new parameters and checks
+    the link.
     """
 
     def __init__(self, n: int, widths: Dict[str, int] = None, device=None, dtype=torch.float32):
@@ -154,6 +157,17 @@ class GradArena:
                 raise RuntimeError(f"view-DP: {name}.grad is not the gradient arena's view (zero_grad(set_to_none="
                                    "True), re-created parameters or a reassigned .grad detach it); call "
                                    "arena.attach(params) again and clear gradients with arena.zero_()")
+
+    def resized(self, n_new: int) -> "GradArena":
+        """A new zeroed arena of `n_new` rows with the same widths, device and dtype.  Gradients are not
+        carried: a resize happens between steps."""
+        return GradArena(n_new, self.widths, device=self.flat.device, dtype=self.flat.dtype)
+
+    def reattach(self, params: Dict[str, torch.Tensor]) -> "GradArena":
+        """`attach`, then `check_attached`: the link is made and verified.  Returns the arena."""
+        self.attach(params)
+        self.check_attached(params)
+        return self
 
     def zero_(self) -> None:
         self.flat.zero_()

@@ -30,7 +30,8 @@
  *                               <- no reference counterpart: local steps of the view-DP exchange
  *                                  (the reference trains on one GPU)
  * INTEGRATION.md shows the Python-side bindings.  Stream compaction and indexed row moves (hidegs_select_flagged,
- * hidegs_gather_rows, hidegs_scatter_rows) are declared in hidegs_rows.h, next to this file.
+ * hidegs_gather_rows, hidegs_scatter_rows) are declared in hidegs_rows.h, next to this file, and resizing by rows
+ * (hidegs_resize_rows) in hidegs_resize.h, which hidegs_rows.h includes.
  */
 #ifndef HIDEGS_H_INCLUDED
 #define HIDEGS_H_INCLUDED

@@ -51,4 +51,8 @@ int hidegs_scatter_rows(const hidegs_row_field* fields, int nfields, const uint3
 #ifdef __cplusplus
 }
 #endif
+
+/* Resizing tensors by rows (prune and append, hidegs_resize_rows): declared in hidegs_resize.h, next to this file. */
+#include "hidegs_resize.h"
+
 #endif /* HIDEGS_ROWS_H_INCLUDED */

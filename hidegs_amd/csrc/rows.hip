@@ -21,6 +21,8 @@
 // Resize (include/hidegs_resize.h): the row surgery of densification -- prune by a keep list, append new
 // rows -- on every per-Gaussian tensor in one launch per kMaxFields.  The same unit stepping over the dense
 // destination, which is written from three sources: kept rows gathered, appended rows copied, or zeros.
+// With include/hidegs_clone.h a fourth: appended rows gathered from the source by a second index list, the
+// clone and the split of densification (resize_rows_cloned_kernel).
 #include <stdint.h>
 
 #include <string>
@@ -290,8 +292,12 @@ struct ResizeBatch {
 // keep[j], or row j itself without a keep array; zeros if that row is past the source); one at or after it
 // comes from append at unit - F.kept, or is zeros.  Which of the two is workgroup-uniform except in the one
 // workgroup that holds unit F.kept.
-template <typename V, bool kKeep>
-__device__ __forceinline__ void resize_units(const ResizeField& F, long long u0, const uint32_t* __restrict__ keep)
+// kClone (include/hidegs_clone.h): the field's appended rows are rows of src too, dst row k + i from src row
+// from[i].  Every unit of dst is then a gathered one; only the index array and the entry differ on the two
+// sides of unit F.kept, so the pointer is selected and one load is issued, as for the data.
+template <typename V, bool kKeep, bool kClone = false>
+__device__ __forceinline__ void resize_units(const ResizeField& F, long long u0, const uint32_t* __restrict__ keep,
+                                             const uint32_t* __restrict__ from_list = nullptr, long long k = 0)
 {
     constexpr uint32_t kUnit = sizeof(V) / sizeof(uint32_t);
     const long long e0 = u0 * kUnit;  // the workgroup's first dst element
@@ -305,7 +311,17 @@ __device__ __forceinline__ void resize_units(const ResizeField& F, long long u0,
     for (int i = 0; i < kUnroll; i++) {  // every index load issued before any is used
         const long long u = u0 + i * kBlock + threadIdx.x;
         // a gathered unit (u < F.kept) has j < k; entry 0 exists (keep is passed only where k >= 1)
-        idx[i] = kKeep ? keep[u < F.kept ? j : 0] : (uint32_t)j;
+        if constexpr (kClone) {
+            // an appended unit (F.kept <= u < F.units) has k <= j < k + n_append; entry 0 of from_list exists
+            // (a field is cloned only where n_append >= 1) and serves the lanes past the last unit
+            const bool gathered = kKeep && u < F.kept;
+            const uint32_t* list = gathered ? keep : from_list;
+            const long long entry = gathered ? j : (u >= F.kept && u < F.units ? j - k : 0);
+            const uint32_t got = list[entry];
+            idx[i] = (!kKeep && u < F.kept) ? (uint32_t)j : got;
+        } else {
+            idx[i] = kKeep ? keep[u < F.kept ? j : 0] : (uint32_t)j;
+        }
         col[i] = c;
         c += F.step_c;
         j += F.step_j;
@@ -319,8 +335,9 @@ __device__ __forceinline__ void resize_units(const ResizeField& F, long long u0,
 #pragma unroll
     for (int i = 0; i < kUnroll; i++) {
         const long long u = u0 + i * kBlock + threadIdx.x;
-        const bool in_src = (u < F.kept) & ((long long)idx[i] < F.n_rows);  // an index past the rows is never dereferenced
-        const bool in_append = (u >= F.kept) & (u < F.units) & (F.append != nullptr);
+        // an index past the rows is never dereferenced
+        const bool in_src = (u < (kClone ? F.units : F.kept)) & ((long long)idx[i] < F.n_rows);
+        const bool in_append = !kClone & (u >= F.kept) & (u < F.units) & (F.append != nullptr);
         const uint32_t* base = in_src ? F.src : (in_append ? F.append : F.safe);
         const size_t at = in_src ? ((size_t)idx[i] * F.width + col[i]) / kUnit : (in_append ? (size_t)(u - F.kept) : 0);
         from[i] = reinterpret_cast<const V*>(base) + at;
@@ -380,6 +397,78 @@ __global__ __launch_bounds__(kBlock) void resize_rows_kernel(const ResizeBatch b
     }
 }
 
+// resize_rows_kernel with a third source for the appended rows (include/hidegs_clone.h): bit f of `cloned` says
+// that field f of the batch takes them from src, row from[i] for dst row k + i.  The mode is workgroup-uniform
+// like the descriptor; the other fields run the code of resize_rows_kernel.
+__global__ __launch_bounds__(kBlock) void resize_rows_cloned_kernel(const ResizeBatch batch,
+                                                                    const uint32_t* __restrict__ keep,
+                                                                    const uint32_t* __restrict__ from, long long k,
+                                                                    uint32_t cloned)
+{
+    ResizeField F = batch.f[0];
+    int first = batch.first[0];
+    bool clone = cloned & 1u;
+#pragma unroll
+    for (int i = 1; i < kMaxFields; i++) {
+        if (i < batch.count && (int)blockIdx.x >= batch.first[i]) {
+            F = batch.f[i];
+            first = batch.first[i];
+            clone = (cloned >> i) & 1u;
+        }
+    }
+    const long long u0 = (long long)((int)blockIdx.x - first) * kUnitsPerBlock;
+    if (!F.safe) {
+        if (F.unit == 4)
+            zero_units<u32x4>(F, u0);
+        else
+            zero_units<uint32_t>(F, u0);
+    } else if (clone) {
+        if (keep) {
+            if (F.unit == 4)
+                resize_units<u32x4, true, true>(F, u0, keep, from, k);
+            else
+                resize_units<uint32_t, true, true>(F, u0, keep, from, k);
+        } else {
+            if (F.unit == 4)
+                resize_units<u32x4, false, true>(F, u0, keep, from, k);
+            else
+                resize_units<uint32_t, false, true>(F, u0, keep, from, k);
+        }
+    } else if (keep) {
+        if (F.unit == 4)
+            resize_units<u32x4, true>(F, u0, keep);
+        else
+            resize_units<uint32_t, true>(F, u0, keep);
+    } else {
+        if (F.unit == 4)
+            resize_units<u32x4, false>(F, u0, keep);
+        else
+            resize_units<uint32_t, false>(F, u0, keep);
+    }
+}
+
+// The descriptor of one field; src and append are NULL where the launch reads no row of theirs.
+ResizeField resize_field(const float* src, const float* append, float* dst, long long n_rows, int width, long long k,
+                         long long n_append)
+{
+    ResizeField F;
+    F.src = reinterpret_cast<const uint32_t*>(src);
+    F.append = reinterpret_cast<const uint32_t*>(append);
+    F.safe = F.src ? F.src : F.append;
+    F.dst = reinterpret_cast<uint32_t*>(dst);
+    F.n_rows = n_rows;
+    F.width = (uint32_t)width;
+    // width a multiple of 4 and every base on 16 bytes: every row start and every quad is aligned, and
+    // k * width is a multiple of 4, so no quad holds both gathered and appended floats
+    F.unit = (width % 4 == 0 && aligned16(F.src) && aligned16(F.append) && aligned16(dst)) ? 4u : 1u;
+    F.kept = k * (long long)width / F.unit;
+    F.units = (k + n_append) * (long long)width / F.unit;
+    F.step_j = (uint32_t)(kBlock * F.unit) / F.width;
+    F.step_c = (uint32_t)(kBlock * F.unit) % F.width;
+    F.inv_w = 1.0 / (double)width;
+    return F;
+}
+
 int resize_rows(const hidegs_resize_field* fields, int nfields, const uint32_t* keep, long long k, long long n_append,
                 hipStream_t stream)
 {
@@ -406,21 +495,8 @@ int resize_rows(const hidegs_resize_field* fields, int nfields, const uint32_t* 
         long long blocks = 0;
         for (int i = i0; i < nfields && i < i0 + kMaxFields; i++) {
             const hidegs_resize_field& a = fields[i];
-            ResizeField F;
-            F.src = reinterpret_cast<const uint32_t*>(k > 0 && a.n_rows > 0 ? a.src : nullptr);
-            F.append = reinterpret_cast<const uint32_t*>(n_append > 0 ? a.append : nullptr);
-            F.safe = F.src ? F.src : F.append;
-            F.dst = reinterpret_cast<uint32_t*>(a.dst);
-            F.n_rows = a.n_rows;
-            F.width = (uint32_t)a.width;
-            // width a multiple of 4 and every base on 16 bytes: every row start and every quad is aligned, and
-            // k * width is a multiple of 4, so no quad holds both gathered and appended floats
-            F.unit = (a.width % 4 == 0 && aligned16(F.src) && aligned16(F.append) && aligned16(a.dst)) ? 4u : 1u;
-            F.kept = k * (long long)a.width / F.unit;
-            F.units = (k + n_append) * (long long)a.width / F.unit;
-            F.step_j = (uint32_t)(kBlock * F.unit) / F.width;
-            F.step_c = (uint32_t)(kBlock * F.unit) % F.width;
-            F.inv_w = 1.0 / (double)a.width;
+            const ResizeField F = resize_field(k > 0 && a.n_rows > 0 ? a.src : nullptr, n_append > 0 ? a.append : nullptr,
+                                               a.dst, a.n_rows, a.width, k, n_append);
             batch.first[batch.count] = (int)blocks;
             batch.f[batch.count++] = F;
             blocks += (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
@@ -430,6 +506,62 @@ int resize_rows(const hidegs_resize_field* fields, int nfields, const uint32_t* 
         HIDEGS_LAUNCH("resize_rows", resize_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch, keep);
     }
     return check_launch("resize_rows", stream, 0);
+}
+
+// hidegs_resize_rows_cloned.  A batch without a cloned field is a launch of resize_rows_kernel itself.
+int resize_rows_cloned(const hidegs_clone_field* fields, int nfields, const uint32_t* keep, long long k,
+                       const uint32_t* from, long long n_append, hipStream_t stream)
+{
+    const std::string who = "resize_rows_cloned";
+    if (nfields < 0) return fail(HIDEGS_E_ARG, who + ": negative field count");
+    if (k < 0 || n_append < 0 || k > kSelectMax || n_append > kSelectMax || k + n_append > kSelectMax)
+        return fail(HIDEGS_E_ARG, who + ": k, n_append and k + n_append must be in [0, 2^31)");
+    if (nfields > 0 && !fields) return fail(HIDEGS_E_ARG, who + ": NULL field list");
+    bool any_cloned = false;
+    for (int i = 0; i < nfields; i++) {
+        const std::string field = who + ": field " + std::to_string(i);
+        if (fields[i].width < 1) return fail(HIDEGS_E_ARG, field + ": width < 1");
+        if (fields[i].n_rows < 0) return fail(HIDEGS_E_ARG, field + ": negative n_rows");
+        if (fields[i].cloned && fields[i].append) return fail(HIDEGS_E_ARG, field + ": cloned, but append is given");
+        any_cloned = any_cloned || fields[i].cloned;
+    }
+    if (k + n_append == 0 || nfields == 0) return 0;
+    const bool cloning = any_cloned && n_append > 0;
+    for (int i = 0; i < nfields; i++) {
+        const hidegs_clone_field& a = fields[i];
+        const bool reads_src = a.n_rows > 0 && (k > 0 || (a.cloned && n_append > 0));
+        if (!a.dst || (reads_src && !a.src))
+            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": NULL pointer");
+        if (!keep && k > a.n_rows)
+            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": without keep, k must not exceed n_rows");
+    }
+    if (cloning && !from) return fail(HIDEGS_E_ARG, who + ": NULL from with a cloned field");
+    if (k == 0) keep = nullptr;  // no row is gathered by keep: the kernel reads no entry
+    for (int i0 = 0; i0 < nfields; i0 += kMaxFields) {  // kMaxFields per launch
+        ResizeBatch batch;
+        batch.count = 0;
+        long long blocks = 0;
+        uint32_t cloned = 0;
+        for (int i = i0; i < nfields && i < i0 + kMaxFields; i++) {
+            const hidegs_clone_field& a = fields[i];
+            const bool clone = a.cloned && n_append > 0;
+            // a cloned field has no append side: 16-byte units where src and dst allow
+            const ResizeField F = resize_field((k > 0 || clone) && a.n_rows > 0 ? a.src : nullptr,
+                                               n_append > 0 ? a.append : nullptr, a.dst, a.n_rows, a.width, k, n_append);
+            if (clone) cloned |= 1u << batch.count;
+            batch.first[batch.count] = (int)blocks;
+            batch.f[batch.count++] = F;
+            blocks += (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
+            if (blocks > 0x7fffffffLL) return fail(HIDEGS_E_ARG, who + ": fields too large for one launch");
+        }
+        batch.first[batch.count] = (int)blocks;
+        if (cloned)
+            HIDEGS_LAUNCH("resize_rows_cloned", resize_rows_cloned_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                          batch, keep, from, k, cloned);
+        else
+            HIDEGS_LAUNCH("resize_rows", resize_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch, keep);
+    }
+    return check_launch("resize_rows_cloned", stream, 0);
 }
 
 }  // namespace
@@ -482,4 +614,11 @@ extern "C" int hidegs_resize_rows(const hidegs_resize_field* fields, int nfields
 {
     if (int rc = hidegs::take_async_error("hidegs_resize_rows", hidegs::as_stream(stream))) return rc;
     return hidegs::resize_rows(fields, nfields, keep, k, n_append, hidegs::as_stream(stream));
+}
+
+extern "C" int hidegs_resize_rows_cloned(const hidegs_clone_field* fields, int nfields, const uint32_t* keep, long long k,
+                                         const uint32_t* from, long long n_append, void* stream)
+{
+    if (int rc = hidegs::take_async_error("hidegs_resize_rows_cloned", hidegs::as_stream(stream))) return rc;
+    return hidegs::resize_rows_cloned(fields, nfields, keep, k, from, n_append, hidegs::as_stream(stream));
 }

@@ -20,6 +20,8 @@ its all-reduce has landed (hidegs_amd.view_dp.ViewDPExchange.exchange_and_step).
 `resize_rows(keep, append, extra)` follows densification: parameters, moments and per-row companions are
 pruned and extended by one launch per 8 tensors (hidegs_amd.resize, csrc/rows.hip), and the parameters and
 `state` are swapped consistently, instead of a boolean index and a cat per tensor on `optimizer.state`.
+With `clone` and `repeats` the appended rows are the parameters' own rows: a clone, or a split with its
+prune, is one such call.
 
 Not supported, as in the reference's masked path, which fails on them with a shape error:
 amsgrad, maximize; capturable (a different op sequence) is not reproduced.
@@ -179,14 +181,20 @@ class Adam(Optimizer):
         return out
 
     @torch.no_grad()
-    def resize_rows(self, keep=None, append=None, extra=None):
+    def resize_rows(self, keep=None, append=None, extra=None, clone=None, repeats=1):
         """Prune and append Gaussians: every group's parameter, its moments and the per-row companions in
         `extra` are resized alike by one `hidegs_amd.resize.resize_rows` call (one host synchronisation).
 
         keep    1-D bool / uint8 device mask over the rows (non-zero: the row stays), or None to keep all.
         append  {group name: new rows}, naming every group (or none): the rows appended to each parameter.
+                With `clone` it may name any subset of the groups, those whose new rows are computed (xyz and
+                scaling in a split); every group it does not name appends its own cloned rows.
         extra   {name: tensor} with one row per Gaussian (the densification statistics): resized by the same
                 `keep`, their appended rows zero.
+        clone   the rows to clone, a mask or an index tensor, and
+        repeats how many times the list is tiled, as in `hidegs_amd.resize.resize_rows`: a clone is
+                `resize_rows(clone=sel)`, a split with prune `resize_rows(keep=~sel, clone=sel, repeats=2,
+                append={"xyz": ..., "scaling": ...})`.  Moments and extras are zero on the appended rows.
         Every group's parameter is replaced by a new nn.Parameter (requires_grad, no .grad) and `self.state` is
         re-keyed to it: exp_avg and exp_avg_sq keep the kept rows and are zero on the appended ones, "step"
         and the group's hyper-parameters are unchanged, a parameter without state gets none.  Bit for bit
@@ -194,7 +202,7 @@ class Adam(Optimizer):
         extras.  Returns (params_by_name, extra_by_name).  A gradient arena has to follow:
         `arena.resized(n_new).reattach(params)` (hidegs_amd.view_dp.GradArena).
         """
-        from hidegs_amd.resize import resize_rows
+        from hidegs_amd.resize import CLONED, resize_rows
 
         named = self._named_params("resize_rows")
         append = dict(append or {})
@@ -203,15 +211,16 @@ class Adam(Optimizer):
         for name in append:
             if name not in names:
                 raise ValueError(f"resize_rows: append names an unknown group {name!r} (groups: {names})")
-        if append:
+        if append and clone is None:
             for name in names:
                 if name not in append:
                     raise ValueError(f"resize_rows: append has no rows for group {name!r}")
-        n_append = None if append else 0  # the appended rows give the count
+        # the appended rows, or the cloned ones, give the count
+        n_append = None if append or clone is not None else 0
         tensors, new_rows, slots = [], [], []
         for name, _, p in named:
             tensors.append(p.detach())
-            new_rows.append(append.get(name))
+            new_rows.append(append.get(name, None if clone is None else CLONED))
             slots.append(("param", name))
             state = self.state.get(p)
             if state:  # lazy initialisation stays: no state, none made
@@ -223,7 +232,7 @@ class Adam(Optimizer):
             tensors.append(t)
             new_rows.append(None)
             slots.append(("extra", name))
-        outs = dict(zip(slots, resize_rows(tensors, keep, new_rows, n_append)))
+        outs = dict(zip(slots, resize_rows(tensors, keep, new_rows, n_append, clone=clone, repeats=repeats)))
         params, extras = {}, {name: outs[("extra", name)] for name in extra}
         for name, group, old in named:
             new = torch.nn.Parameter(outs[("param", name)], requires_grad=True)

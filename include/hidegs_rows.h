@@ -54,5 +54,7 @@ int hidegs_scatter_rows(const hidegs_row_field* fields, int nfields, const uint3
 
 /* Resizing tensors by rows (prune and append, hidegs_resize_rows): declared in hidegs_resize.h, next to this file. */
 #include "hidegs_resize.h"
+/* The same with appended rows cloned from the tensor itself (hidegs_resize_rows_cloned): hidegs_clone.h. */
+#include "hidegs_clone.h"
 
 #endif /* HIDEGS_ROWS_H_INCLUDED */

@@ -117,6 +117,42 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t v)
     return (uint32_t)x;
 }
 
+// Reduction of one u32 per lane over the 64 lanes by an idempotent operation (min, max, and, or), with
+// the same DPP moves: row_shr:1/2/4/8 leave each row's result in its lane 15, row_bcast:15 and
+// row_bcast:31 carry it on to lane 63, which is read back as a wave-uniform value.  A lane with no
+// source keeps its own value (op(x, x) == x), so no identity is needed.  Seven VALU steps and a
+// v_readlane where the __shfl_xor chain takes six ds_bpermute round trips.  Every lane of the wave must
+// be active.
+#define HIDEGS_DPP_SELF(x, ctrl, rows) ((uint32_t)__builtin_amdgcn_update_dpp((int)(x), (int)(x), ctrl, rows, 0xf, false))
+template <typename Op>
+__device__ __forceinline__ uint32_t wave_reduce_u32(uint32_t x, Op op)
+{
+    x = op(x, HIDEGS_DPP_SELF(x, 0x111, 0xf));  // row_shr:1
+    x = op(x, HIDEGS_DPP_SELF(x, 0x112, 0xf));  // row_shr:2
+    x = op(x, HIDEGS_DPP_SELF(x, 0x114, 0xf));  // row_shr:4
+    x = op(x, HIDEGS_DPP_SELF(x, 0x118, 0xf));  // row_shr:8
+    x = op(x, HIDEGS_DPP_SELF(x, 0x142, 0xa));  // row_bcast:15 into rows 1 and 3
+    x = op(x, HIDEGS_DPP_SELF(x, 0x143, 0xc));  // row_bcast:31 into rows 2 and 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, kWave - 1);
+}
+#undef HIDEGS_DPP_SELF
+struct OpMinU32 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; }
+};
+struct OpMaxU32 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
+};
+struct OpAndU32 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a & b; }
+};
+struct OpOrU32 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; }
+};
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_reduce_u32(v, OpMinU32()); }
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return wave_reduce_u32(v, OpMaxU32()); }
+__device__ __forceinline__ uint32_t wave_and_u32(uint32_t v) { return wave_reduce_u32(v, OpAndU32()); }
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) { return wave_reduce_u32(v, OpOrU32()); }
+
 __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll

@@ -102,22 +102,17 @@ __device__ __forceinline__ uint32_t lds_rank(const uint32_t* a, uint32_t n, uint
     return lo;
 }
 
+// Every lane gets the wave's result (wave_reduce_u32: DPP moves, all lanes active).
 __device__ __forceinline__ void wave_and_or(uint32_t& a, uint32_t& o)
 {
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        a &= __shfl_xor(a, sh, kWave);
-        o |= __shfl_xor(o, sh, kWave);
-    }
+    a = wave_and_u32(a);
+    o = wave_or_u32(o);
 }
 
 __device__ __forceinline__ void wave_min_max(uint32_t& lo, uint32_t& hi)
 {
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor(lo, sh, kWave));
-        hi = max(hi, (uint32_t)__shfl_xor(hi, sh, kWave));
-    }
+    lo = wave_min_u32(lo);
+    hi = wave_max_u32(hi);
 }
 
 // LDS of the oversized-segment forms (the one-workgroup global form, the partition jobs).
@@ -371,6 +366,7 @@ constexpr int kBuckets = 1 << kBucketBits;
 constexpr int kMaxBucket = 128;  // a fuller bucket sends the segment to the LSD form
 constexpr int kIndexBits = 11;   // index in segment < kSegCap
 constexpr int kSegWaves = 7;  // waves per SIMD segment_sort_kernel's register budget is set for (17 KB of LDS allows 9)
+constexpr int kSegWavesPacked = 8;  // ... and of its Packed instance (the tile sort's), which holds no high key halves
 
 static_assert(kSegCap <= (1 << kIndexBits), "segment index must fit its field");
 
@@ -420,6 +416,65 @@ __device__ __forceinline__ SegStats segment_stats(uint32_t a, uint32_t o, uint32
     st.dbits = nbits < kBucketBits ? nbits : kBucketBits;
     st.shift = nbits - st.dbits;
     return st;
+}
+
+// What the bucket form itself needs of those, in one round: each wave's MIN / MAX into LDS behind one
+// barrier (which also orders the caller's zeroing of the bucket counters).  lo == hi: equal low keys.
+// s0, s1 (kWavesPerBlock words each) must be free on entry and hold the waves' values afterwards.
+struct SegRange {
+    uint32_t lo, hi;
+    int shift;
+};
+__device__ __forceinline__ SegRange segment_range(uint32_t lo, uint32_t hi, uint32_t* s0, uint32_t* s1)
+{
+    const int lane = lane_id(), wave = threadIdx.x / kWave;
+    wave_min_max(lo, hi);
+    if (lane == 0) {
+        s0[wave] = lo;
+        s1[wave] = hi;
+    }
+    __syncthreads();
+    SegRange r;
+    r.lo = 0xffffffffu;
+    r.hi = 0u;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; w++) {
+        r.lo = min(r.lo, s0[w]);
+        r.hi = max(r.hi, s1[w]);
+    }
+    const int nbits = r.hi > r.lo ? 32 - __builtin_clz(r.hi - r.lo) : 0;
+    r.shift = nbits - (nbits < kBucketBits ? nbits : kBucketBits);
+    return r;
+}
+
+// The low key bits that vary over the segment (AND ^ OR), for the LSD form: computed on the way into it
+// from the pairs still in registers, the bucket form having no use for them.  s0, s1 must be free on
+// entry; the barrier inside is the one the LSD form needs before it reuses the bucket form's LDS.
+__device__ __forceinline__ uint32_t segment_diff(const uint64_t (&k)[kSegItems], const uint32_t m, uint32_t* s0,
+                                                 uint32_t* s1)
+{
+    const int lane = lane_id(), wave = threadIdx.x / kWave;
+    uint32_t a = 0xffffffffu, o = 0u;
+#pragma unroll
+    for (int q = 0; q < kSegItems; q++) {
+        if (threadIdx.x + q * kBlock < m) {
+            a &= (uint32_t)k[q];
+            o |= (uint32_t)k[q];
+        }
+    }
+    wave_and_or(a, o);
+    if (lane == 0) {
+        s0[wave] = a;
+        s1[wave] = o;
+    }
+    __syncthreads();
+    uint32_t aa = 0xffffffffu, oo = 0u;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; w++) {
+        aa &= s0[w];
+        oo |= s1[w];
+    }
+    return aa ^ oo;
 }
 
 

@@ -26,15 +26,15 @@ union QueueLds {
 // and 4 (fill and rank) are written out in both: as a shared helper they cost piece_sort_kernel a
 // spilled VGPR (8 B/lane of scratch).
 
-// The segment's pairs into registers, with the AND / OR / MIN / MAX of their low halves and hd, the
-// OR of (high half ^ ref_hi): nonzero when any pair's high half differs from the first pair's.
+// The segment's pairs into registers, with the MIN / MAX of their low halves and hd, the OR of
+// (high half ^ ref_hi): nonzero when any pair's high half differs from the first pair's.
 // Packed: src_k holds {low key half, value} records (radix_scatter_kernel's Packed output) and every
-// high half is ref_hi, the segment id; src_v is not read.
+// high half is ref_hi, the segment id; src_v is not read and hd is left alone.
 template <bool Packed = false>
 __device__ __forceinline__ void seg_load(const uint64_t* __restrict__ src_k, const uint32_t* __restrict__ src_v,
                                          const uint32_t begin, const uint32_t m, const uint32_t ref_hi,
-                                         uint64_t (&k)[kSegItems], uint32_t (&v)[kSegItems], uint32_t& a, uint32_t& o,
-                                         uint32_t& lo, uint32_t& hi, uint32_t& hd)
+                                         uint64_t (&k)[kSegItems], uint32_t (&v)[kSegItems], uint32_t& lo, uint32_t& hi,
+                                         uint32_t& hd)
 {
     const int t = threadIdx.x;
 #pragma unroll
@@ -50,11 +50,9 @@ __device__ __forceinline__ void seg_load(const uint64_t* __restrict__ src_k, con
                 v[q] = src_v[begin + i];
             }
             const uint32_t x = (uint32_t)k[q];
-            a &= x;
-            o |= x;
             lo = min(lo, x);
             hi = max(hi, x);
-            hd |= (uint32_t)(k[q] >> 32) ^ ref_hi;
+            if (!Packed) hd |= (uint32_t)(k[q] >> 32) ^ ref_hi;
         }
     }
 }
@@ -75,7 +73,9 @@ __device__ __forceinline__ void store_loaded(const uint64_t (&k)[kSegItems], con
 
 // Steps 1 and 2: the bucket histogram (bucket = (x - base_lo) >> shift, over the segment's key range; sh.fill
 // zeroed by the caller), the bucket starts into sh.start and sh.fill.  Returns the fullest bucket's
-// count; mixed_hi: whether any thread's hd is nonzero.
+// count; mixed_hi: whether any thread's hd is nonzero (OneHi: no pair's is, by construction -- hd is
+// not looked at).
+template <bool OneHi = false>
 __device__ __forceinline__ uint32_t bucket_starts(const uint64_t (&k)[kSegItems], const uint32_t m,
                                                   const uint32_t base_lo, const int shift, const uint32_t hd,
                                                   BucketShared& sh, uint32_t* s_and, uint32_t* s_max,
@@ -96,13 +96,13 @@ __device__ __forceinline__ uint32_t bucket_starts(const uint64_t (&k)[kSegItems]
     }
     uint32_t dummy;
     uint32_t pre = block_exclusive_scan(sum, s_max, &dummy);  // its barriers order the reads above
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const uint32_t y = __shfl_xor(mx, s, kWave);
-        mx = y > mx ? y : mx;
+    mx = wave_max_u32(mx);
+    if (OneHi) {
+        if (lane == 0) s_and[wave] = mx;
+    } else {
+        const bool wave_hd = __ballot(hd != 0u) != 0ull;
+        if (lane == 0) s_and[wave] = mx | (wave_hd ? 0x80000000u : 0u);  // mx <= kSegCap: bit 31 is free
     }
-    const bool wave_hd = __ballot(hd != 0u) != 0ull;
-    if (lane == 0) s_and[wave] = mx | (wave_hd ? 0x80000000u : 0u);  // mx <= kSegCap: bit 31 is free
 #pragma unroll
     for (int j = 0; j < kBuckets / kBlock; j++) {
         sh.start[t * (kBuckets / kBlock) + j] = pre;
@@ -114,9 +114,9 @@ __device__ __forceinline__ uint32_t bucket_starts(const uint64_t (&k)[kSegItems]
     mixed_hi = 0;
 #pragma unroll
     for (int w = 0; w < kWavesPerBlock; w++) {
-        const uint32_t f = s_and[w] & 0x7fffffffu;
+        const uint32_t f = OneHi ? s_and[w] : s_and[w] & 0x7fffffffu;
         fullest = f > fullest ? f : fullest;
-        mixed_hi |= s_and[w] >> 31;
+        if (!OneHi) mixed_hi |= s_and[w] >> 31;
     }
     return fullest;
 }
@@ -124,31 +124,28 @@ __device__ __forceinline__ uint32_t bucket_starts(const uint64_t (&k)[kSegItems]
 // Step 5 stages (key, value) by final position in LDS, then stores the segment contiguously (stores
 // straight from registers scatter 8- and 4-byte writes over the segment: 78 -> 50 us at 8M pairs).
 // Both forms follow a barrier after the ranking: the staging reuses sh.
-// Compact form, one high half (ref_hi) for the whole segment: the low halves and the values, (4 + 4) B
-// per pair, so a segment of up to kSegCap pairs goes through LDS in one pass; the keys are rebuilt on store.
+// Compact form, one high half (ref_hi) for the whole segment: {low half, value} records, 8 B per pair in
+// one LDS write at its final position and one read, so a segment of up to kSegCap pairs goes through LDS
+// in one pass; the keys are rebuilt on store.
 __device__ __forceinline__ void stage_compact(const uint64_t (&k)[kSegItems], const uint32_t (&v)[kSegItems],
                                               const uint32_t (&pos)[kSegItems], const uint32_t begin,
                                               const uint32_t m, const uint32_t ref_hi, BucketShared& sh, uint64_t* dk,
                                               uint32_t* dv)
 {
     const int t = threadIdx.x;
-    uint32_t* stage_lo = reinterpret_cast<uint32_t*>(&sh);
-    uint32_t* stage_vv = stage_lo + kSegCap;
+    uint2* stage = reinterpret_cast<uint2*>(&sh);
 #pragma unroll
-    for (int q = 0; q < kSegItems; q++) {
-        if (t + q * kBlock < m) {
-            stage_lo[pos[q]] = (uint32_t)k[q];
-            stage_vv[pos[q]] = v[q];
-        }
-    }
+    for (int q = 0; q < kSegItems; q++)
+        if (t + q * kBlock < m) stage[pos[q]] = make_uint2((uint32_t)k[q], v[q]);
     __syncthreads();
     const uint64_t khi = (uint64_t)ref_hi << 32;
 #pragma unroll
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = t + q * kBlock;
         if (i < m) {
-            dk[begin + i] = khi | stage_lo[i];
-            dv[begin + i] = stage_vv[i];
+            const uint2 rec = stage[i];
+            dk[begin + i] = khi | rec.x;
+            dv[begin + i] = rec.y;
         }
     }
 }
@@ -207,15 +204,14 @@ __device__ __forceinline__ void sort_segment(const uint64_t* __restrict__ src_k,
     const int t = threadIdx.x;
     uint64_t k[kSegItems];
     uint32_t v[kSegItems];
-    uint32_t a = 0xffffffffu, o = 0, lo = 0xffffffffu, hi = 0;
+    uint32_t lo = 0xffffffffu, hi = 0;
     const uint32_t ref_hi = m ? (uint32_t)(src_k[begin] >> 32) : 0u;  // see segment_sort_kernel (m == 0: no read)
     uint32_t hd = 0;
-    seg_load(src_k, src_v, begin, m, ref_hi, k, v, a, o, lo, hi, hd);
+    seg_load(src_k, src_v, begin, m, ref_hi, k, v, lo, hi, hd);
     BucketShared& sh = lds.bucket;
     for (int i = t; i < kBuckets; i += kBlock) sh.fill[i] = 0u;
-    const SegStats st = segment_stats(a, o, lo, hi, s_and, s_or);
-    const uint32_t diff = st.diff;  // low key bits that vary over the segment
-    if (diff == 0) {  // equal low keys: the input order is the stable order
+    const SegRange st = segment_range(lo, hi, s_and, s_or);
+    if (st.lo == st.hi) {  // equal low keys: the input order is the stable order
         if (!InPlace) {
 #pragma unroll
             for (int q = 0; q < kSegItems; q++) {
@@ -233,7 +229,7 @@ __device__ __forceinline__ void sort_segment(const uint64_t* __restrict__ src_k,
     const uint32_t fullest = bucket_starts(k, m, st.lo, shift, hd, sh, s_and, s_max, mixed_hi);
     if (fullest > (uint32_t)kMaxBucket || shift + kIndexBits > 32) {  // crowded depths, or fields too
         // wide for 32 bits: the LSD form (block-uniform branch)
-        __syncthreads();
+        const uint32_t diff = segment_diff(k, m, s_max, s_or);  // (s_and is still being read; these two are free)
         segment_sort_lsd<InPlace>(src_k, src_v, dst_k, dst_v, begin, m, diff, lds.lsd);
         return;
     }
@@ -375,9 +371,9 @@ __device__ __forceinline__ void expand_records(uint64_t* keys, uint32_t* vals, c
 // whole keys and values behind; a segment that this kernel does not sort itself is expanded in place
 // by its own workgroup first, so the queue's kernels and the one-workgroup forms see ordinary pairs.
 template <bool Packed>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kSegWaves))) void segment_sort_kernel(
-    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, const uint32_t* __restrict__ starts,
-    uint2* __restrict__ ranges_out, const int nseg, const BigQueue q)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Packed ? kSegWavesPacked : kSegWaves)))
+void segment_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, const uint32_t* __restrict__ starts,
+                         uint2* __restrict__ ranges_out, const int nseg, const BigQueue q)
 {
     __shared__ __attribute__((aligned(16))) SegLds lds;
     __shared__ uint32_t s_and[kWavesPerBlock], s_or[kWavesPerBlock], s_max[kWavesPerBlock];
@@ -470,56 +466,61 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kSegWave
     const int t = threadIdx.x;
     uint64_t k[kSegItems];
     uint32_t v[kSegItems];
-    uint32_t a = 0xffffffffu, o = 0, lo = 0xffffffffu, hi = 0;
+    uint32_t lo = 0xffffffffu, hi = 0;
     // the segment's first high key half: the segment id (tile), and with no bits above end_bit -- as
     // hidegs_sort_tile_pairs' callers guarantee -- every pair's high half; `hd` records any that differs
-    // (Packed: the segment id itself, with no load to wait for)
+    // (Packed: the segment id itself, with no load to wait for, and nothing to record)
     const uint32_t ref_hi = Packed ? seg : (uint32_t)(keys[begin] >> 32);
     uint32_t hd = 0;
-    seg_load<Packed>(keys, vals, begin, m, ref_hi, k, v, a, o, lo, hi, hd);
+    seg_load<Packed>(keys, vals, begin, m, ref_hi, k, v, lo, hi, hd);
     BucketShared& sh = lds.bucket;
     for (int i = t; i < kBuckets; i += kBlock) sh.fill[i] = 0u;
-    const SegStats st = segment_stats(a, o, lo, hi, s_and, s_or);
-    const uint32_t diff = st.diff;  // low key bits that vary over the segment
-    if (diff == 0) {  // equal low keys: the input order is the stable order
-        // (read again, not stored from k and v: keeping those live to here costs 28 B/lane of scratch)
+    const SegRange st = segment_range(lo, hi, s_and, s_or);
+    if (st.lo == st.hi) {  // equal low keys: the input order is the stable order
+        // (read again, not stored from k and v: keeping those live to here costs scratch)
         if (Packed) expand_records(keys, vals, begin, m, seg);
         return;
     }
     const int shift = st.shift;
     uint32_t mixed_hi;
-    const uint32_t fullest = bucket_starts(k, m, st.lo, shift, hd, sh, s_and, s_max, mixed_hi);
+    const uint32_t fullest = bucket_starts<Packed>(k, m, st.lo, shift, hd, sh, s_and, s_max, mixed_hi);
     if (fullest > (uint32_t)kMaxBucket || shift + kIndexBits > 32) {  // crowded depths, or fields too
         // wide for 32 bits: the LSD form (block-uniform branch), which reads whole pairs
         if (Packed) store_loaded(k, v, begin, m, keys, vals);
-        __syncthreads();
+        // the bits that vary, from the registers; its barrier also publishes the pairs just stored
+        // (s_and is still being read; s_max and s_or are free)
+        const uint32_t diff = segment_diff(k, m, s_max, s_or);
         segment_sort_lsd<true>(keys, vals, nullptr, nullptr, begin, m, diff, lds.lsd);
         return;
     }
     const uint32_t base_lo = st.lo;
     const uint32_t lowmask = (uint32_t)((1ull << shift) - 1ull);
     // 3. fill the buckets in any order
-    uint32_t me[kSegItems];
-    uint32_t bucket[kSegItems];
 #pragma unroll
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = t + q * kBlock;
         if (i < m) {
             const uint32_t x = (uint32_t)k[q] - base_lo;
-            bucket[q] = x >> shift;
-            me[q] = ((x & lowmask) << kIndexBits) | i;
-            sh.comb[atomicAdd(&sh.fill[bucket[q]], 1u)] = me[q];
+            sh.comb[atomicAdd(&sh.fill[x >> shift], 1u)] = ((x & lowmask) << kIndexBits) | i;
         }
     }
     __syncthreads();
-    // 4. exact rank inside the bucket
+    // 4. exact rank inside the bucket.  The bucket and the (low bits, index) word are worked out again
+    // from the low key half (three VALU instructions) and not held over the barrier: 16 VGPRs, which
+    // the 8-waves-per-SIMD budget of the Packed instance does not have.  The empty asm keeps the
+    // compiler from reusing the fill step's values.
     uint32_t pos[kSegItems];
 #pragma unroll
     for (int q = 0; q < kSegItems; q++) {
-        if (t + q * kBlock < m) {
-            const uint32_t s0 = sh.start[bucket[q]], e0 = sh.fill[bucket[q]];
+        const uint32_t i = t + q * kBlock;
+        if (i < m) {
+            uint32_t x = (uint32_t)k[q];
+            asm volatile("" : "+v"(x));
+            x -= base_lo;
+            const uint32_t b = x >> shift, me = ((x & lowmask) << kIndexBits) | i;
+            const uint32_t s0 = sh.start[b], e0 = sh.fill[b];
             uint32_t rank = 0;
-            for (uint32_t j = s0; j < e0; j++) rank += sh.comb[j] < me[q] ? 1u : 0u;
+            for (uint32_t j = s0; j < e0; j++) rank += sh.comb[j] < me ? 1u : 0u;
             pos[q] = s0 + rank;
         }
     }

@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/hidegs.h, include/hidegs_rows.h, include/hidegs_resize.h and
-include/hidegs_clone.h (hidegs_amd/libhidegs.so).
+"""ctypes binding of the C ABI in include/hidegs.h, include/hidegs_rows.h, include/hidegs_resize.h,
+include/hidegs_clone.h and include/hidegs_topk.h (hidegs_amd/libhidegs.so).
 
 This is the only place that loads the native library.  It fails loudly: a missing
 library raises ImportError-like RuntimeError at first use, and a non-zero return
@@ -120,18 +120,25 @@ CLONE_SIGNATURES = {
     "hidegs_resize_rows_cloned": (I, [P, I, P, LL, P, LL, P]),
 }
 
+# include/hidegs_topk.h
+TOPK_SIGNATURES = {
+    "hidegs_top_k_scratch_bytes": (SZ, [LL]),
+    "hidegs_top_k_mask_f32": (I, [P, SZ, P, P, LL, LL, P, P, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
 
 def load_library(path: str) -> C.CDLL:
-    """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h, hidegs_resize.h and
-    hidegs_clone.h bound (lib() for the product build; tests load the build.VARIANTS this way)."""
+    """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h, hidegs_resize.h,
+    hidegs_clone.h and hidegs_topk.h bound (lib() for the product build; tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
                            "(or __graft_entry__.build()) to compile it for gfx950")
     dll = C.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES, **CLONE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES, **CLONE_SIGNATURES,
+                              **TOPK_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,5 @@
-"""Torch-facing wrappers of the binning primitives in include/hidegs.h, and of the stream compaction
-of include/hidegs_rows.h.
+"""Torch-facing wrappers of the binning primitives in include/hidegs.h, of the stream compaction of
+include/hidegs_rows.h and of the top-k row selection of include/hidegs_topk.h.
 
 These are the stages between preprocess and render in Rasterizer::forward
 (rasterizer_impl.cu:321-371): inclusive scan of tiles_touched, the stable radix sort
@@ -75,6 +75,72 @@ def select_flagged(mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
                                      count.data_ptr(), _lib.stream_handle(dev))
         _lib.check(rc, "select_flagged")
     return indices, count
+
+
+def _need_mask(t, what: str, n: int) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"top_k_mask: {what} is not a tensor")
+    if t.dtype not in (torch.bool, torch.uint8) or t.dim() != 1 or not t.is_contiguous():
+        raise RuntimeError(f"top_k_mask: {what}: expected a contiguous 1-D bool or uint8 mask, got {t.dtype} "
+                           f"of shape {tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    if t.numel() != n:
+        raise RuntimeError(f"top_k_mask: {what} has {t.numel()} entries, scores has {n}")
+
+
+def top_k_mask(scores: torch.Tensor, k: int, among: torch.Tensor = None,
+               out: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k row selection (include/hidegs_topk.h): the mask of the min(k, candidates) best-scored candidate
+    rows.  A radix select on the GPU: no sort, no host synchronisation, and a defined order.
+
+    scores: 1-D contiguous float32 GPU tensor.  among: optional 1-D bool / uint8 mask of the same length on the
+    same device; a row is a candidate where it is non-zero (every row without it).  k: a non-negative int.
+    out: optional bool / uint8 tensor of the same length that receives the mask; it may be `among` itself.
+
+    Rows rank by descending score, then ascending row index; -0.0 counts as +0.0 and a NaN ranks below -inf,
+    so a NaN score never displaces a number.  The result depends on (scores, among, k) alone: replicas that
+    hold the same scores select the same rows.
+
+    Returns (mask, info).  mask is a torch.bool tensor (a view of `out` where that is given) with exactly
+    min(k, candidates) entries set.  info is a 4-entry int32 device tensor: the number selected, the number
+    of candidates, the bits of the threshold score (the lowest selected score; 0 when nothing is selected) and
+    how many rows of exactly that score are selected.  The threshold as a float:
+    `info[2:3].view(torch.float32)`.  Reading info on the host synchronises; the call does not.
+    """
+    if not isinstance(scores, torch.Tensor):
+        raise RuntimeError("top_k_mask: scores is not a tensor")
+    if scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous():
+        raise RuntimeError(f"top_k_mask: scores: expected a contiguous 1-D float32 tensor, got {scores.dtype} "
+                           f"of shape {tuple(scores.shape)}{'' if scores.is_contiguous() else ' (not contiguous)'}")
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise RuntimeError(f"top_k_mask: k must be a non-negative int, got {k!r}")
+    n = scores.numel()
+    if n >= 1 << 31:
+        raise RuntimeError("top_k_mask: at most 2^31 - 1 rows")
+    if among is not None:
+        _need_mask(among, "among", n)
+    if out is not None:
+        _need_mask(out, "out", n)
+    for what, t in (("scores", scores), ("among", among), ("out", out)):
+        if t is not None and t.device.type != "cuda":
+            raise RuntimeError(f"top_k_mask: {what}: expected a GPU tensor, got one on {t.device}")
+        if t is not None and t.device != scores.device:
+            raise RuntimeError(f"top_k_mask: tensors on different devices: scores on {scores.device}, {what} on "
+                               f"{t.device}")
+    dev = scores.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(n, dtype=torch.bool, device=dev)
+        mask = out if out.dtype == torch.bool else out.view(torch.bool)
+        if n == 0:
+            return mask, torch.zeros(4, dtype=torch.int32, device=dev)
+        info = torch.empty(4, dtype=torch.int32, device=dev)
+        L = _lib.lib()
+        tmp = _scratch(L.hidegs_top_k_scratch_bytes(n), dev)
+        rc = L.hidegs_top_k_mask_f32(tmp.data_ptr(), tmp.numel(), scores.data_ptr(),
+                                     None if among is None else among.data_ptr(), n, min(k, (1 << 31) - 1),
+                                     out.data_ptr(), info.data_ptr(), _lib.stream_handle(dev))
+        _lib.check(rc, "top_k_mask")
+    return mask, info
 
 
 def sort_pairs(keys: torch.Tensor, values: torch.Tensor, begin_bit: int = 0,

@@ -1,5 +1,5 @@
 """Build recipe for hidegs_amd/libhidegs.so (the C-ABI library of include/hidegs.h, hidegs_rows.h,
-hidegs_resize.h, hidegs_clone.h and hidegs_topk.h).
+hidegs_resize.h, hidegs_clone.h, hidegs_topk.h and hidegs_nearest.h).
 
 Built in-tree with hipcc for gfx950 so the .so travels to the GPU box with the
 repository snapshot.  `python -m hidegs_amd.build` or `__graft_entry__.build()`.
@@ -27,13 +27,15 @@ INCLUDE = os.path.join(HERE, "..", "include")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhidegs.so")
 VARIANT_DIR = os.path.join(HERE, "variants")
-SOURCES = ["abi.cpp", "timing.cpp", "primitives.hip", "knn.hip", "adam.hip", "wire.hip", "rows.hip", "topk.hip"]
+SOURCES = ["abi.cpp", "timing.cpp", "primitives.hip", "knn.hip", "adam.hip", "wire.hip", "rows.hip", "topk.hip",
+           "nearest.hip"]
 # every header: a change to any of them rebuilds every object
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "hidegs.h"),
                                                          os.path.join(INCLUDE, "hidegs_rows.h"),
                                                          os.path.join(INCLUDE, "hidegs_resize.h"),
                                                          os.path.join(INCLUDE, "hidegs_clone.h"),
-                                                         os.path.join(INCLUDE, "hidegs_topk.h")]
+                                                         os.path.join(INCLUDE, "hidegs_topk.h"),
+                                                         os.path.join(INCLUDE, "hidegs_nearest.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf, so the
 # oracle (oracle/knn_ref.c) can reproduce each rounding step bit for bit.

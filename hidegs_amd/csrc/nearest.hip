@@ -1,0 +1,712 @@
+// nearest.hip -- nearest-point index (include/hidegs_nearest.h): built once over a (P,3) cloud, then asked for
+// the nearest point of arbitrary query positions.  Exact: the candidate minimising (bits(d), row index).
+//
+// Build (the structure distCUDA2 searches, knn.hip, kept in a caller-owned buffer; the builders below
+// resemble knn.hip's on purpose -- that file is closed, and folding both onto one header is a later change):
+//   1. bounding box over the finite rows (grid-stride partials + one finishing workgroup), no host read;
+//   2. 48-bit Morton keys (16 bits per axis), kept below the largest, which the rows with a non-finite
+//      coordinate take alone: they sort strictly last;
+//   3. stable radix sort (sort_pairs_u64);
+//   4. gather into float4 {x, y, z, bits(row)}; a non-candidate row is stored as three NaNs, so its distance
+//      is a NaN, whose bits are above +inf's: it can never win and it widens no box;
+//   5. leaf AABBs over kLeaf = 64 consecutive sorted points, super-box AABBs over kFan = 64 leaves, and each
+//      leaf's first key.  The frame (box origin and scale) is kept in the index for the queries' keys.
+//
+// Query:
+//   1. key the queries in the index's frame (clamped into the box) and sort (key, j): the 64 queries of a
+//      wave are neighbours in space.  The order is for coherence only; results go to position j.
+//   2. phase 1, one wave per 64 sorted queries: every lane's best is seeded from the leaf where the wave's
+//      median key falls and its two Morton neighbours (candidates broadcast by v_readlane); super-boxes and
+//      then leaves are tested against the wave's query AABB and the largest lane bound; the passing leaves
+//      are listed in LDS and evaluated with each lane's own bound as the fine filter.
+//   3. a wave whose list would grow past kBailout leaves, or whose first and last key lie more than kSpanBail
+//      leaves apart to begin with, hands its queries to the hard list (one atomic counter); phase 2, a
+//      second launch, searches each with one wave: lanes over candidates, a wave min.
+//
+// A lane's best is one u64, bits(d) << 32 | row, kept by an unsigned min: the contract's order itself.
+// Exactness: every lower bound is the distance's own monotone expression applied to componentwise smaller
+// gaps, and a box or point is skipped only when its bound is strictly above an upper bound of the best
+// distance of every query it is skipped for -- an equal bound may hide an equal distance at a lower row.
+// Seeds, ordering and the bail-out change the speed only.  All distances and bounds are non-negative
+// floats (or +inf), so they are compared as unsigned integers.
+#include <float.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/hidegs_nearest.h"
+#include "common.h"
+
+namespace hidegs {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / kWave;  // 4
+constexpr int kLeaf = 64;               // points per leaf
+constexpr int kFan = 64;                // leaves per super-box
+constexpr int kMortonBits = 16;         // per axis
+constexpr int kBoundBlocks = 1024;
+constexpr int kListCap = 256;           // candidate leaves buffered per wave
+constexpr int kBailout = 256;           // candidate leaves after which a wave hands its queries to phase 2
+constexpr int kSpanBail = 16;           // leaves between a wave's first and last key above which it does so unseeded
+constexpr int kHardGrid = 4096;         // workgroups of phase 2 at most
+constexpr long long kNearestMax = 0x7fffffffLL;
+constexpr uint32_t kInfBits = 0x7f800000u;
+constexpr uint64_t kLastKey = 0xffffffffffffull;  // of a non-candidate row
+static_assert(kLeaf == kWave, "one lane per point of a leaf");
+static_assert(kBailout <= kListCap, "the list holds every leaf of a wave that does not bail");
+
+struct Box {
+    float4 lo, hi;
+};
+
+struct Counters {
+    uint32_t hard;  // queries sent to phase 2: the first word of the query scratch
+};
+
+inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
+
+__device__ __forceinline__ bool finite3(float x, float y, float z)
+{
+    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for a NaN
+}
+
+__device__ __forceinline__ float sqdist(float4 q, float4 c)
+{
+    const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
+    return fmaf(dz, dz, fmaf(dx, dx, dy * dy));
+}
+
+// Bits of a lower bound of sqdist(q, c) over c in the box: the same monotone expression.
+__device__ __forceinline__ uint32_t box_point_lb(const Box& b, float4 q)
+{
+    const float gx = fmaxf(fmaxf(b.lo.x - q.x, q.x - b.hi.x), 0.f);
+    const float gy = fmaxf(fmaxf(b.lo.y - q.y, q.y - b.hi.y), 0.f);
+    const float gz = fmaxf(fmaxf(b.lo.z - q.z, q.z - b.hi.z), 0.f);
+    return __float_as_uint(fmaf(gz, gz, fmaf(gx, gx, gy * gy)));
+}
+
+// The same over every query in the AABB [qlo, qhi].
+__device__ __forceinline__ uint32_t box_box_lb(const Box& b, float4 qlo, float4 qhi)
+{
+    const float gx = fmaxf(fmaxf(b.lo.x - qhi.x, qlo.x - b.hi.x), 0.f);
+    const float gy = fmaxf(fmaxf(b.lo.y - qhi.y, qlo.y - b.hi.y), 0.f);
+    const float gz = fmaxf(fmaxf(b.lo.z - qhi.z, qlo.z - b.hi.z), 0.f);
+    return __float_as_uint(fmaf(gz, gz, fmaf(gx, gx, gy * gy)));
+}
+
+__device__ __forceinline__ float uniform_lane(float v, int src)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
+__device__ __forceinline__ uint64_t pack(float d, float row_bits)
+{
+    return ((uint64_t)__float_as_uint(d) << 32) | __float_as_uint(row_bits);
+}
+
+// Upper bound of a best's distance, as bits: +inf while nothing (or only an overflowed distance) was found.
+__device__ __forceinline__ uint32_t bound_bits(uint64_t best) { return min((uint32_t)(best >> 32), kInfBits); }
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
+{
+    const uint32_t hi = (uint32_t)(v >> 32);
+    const uint32_t mh = wave_min_u32(hi);
+    const uint32_t ml = wave_min_u32(hi == mh ? (uint32_t)v : 0xffffffffu);
+    return ((uint64_t)mh << 32) | ml;
+}
+
+__device__ __forceinline__ uint64_t lanes_below(int lane) { return (lane == 0) ? 0ull : (~0ull >> (64 - lane)); }
+
+__device__ __forceinline__ uint64_t spread3(uint32_t v)
+{
+    // bit i of v -> bit 3i (v < 2^21)
+    uint64_t x = v & 0x1fffffu;
+    x = (x | (x << 32)) & 0x001f00000000ffffull;
+    x = (x | (x << 16)) & 0x001f0000ff0000ffull;
+    x = (x | (x << 8)) & 0x100f00f00f00f00full;
+    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
+    x = (x | (x << 2)) & 0x1249249249249249ull;
+    return x;
+}
+
+// Morton key of a position in the frame {lo.xyz, scale.xyz}, clamped into the box (a NaN goes to 0) and kept
+// below kLastKey: the non-candidate rows alone have that key, so they sort strictly last, behind every
+// candidate, and no query's key -- one beyond the box's far corner included -- falls into a leaf that holds
+// only them (find_leaf then seeds from the last leaf with a candidate).  The key orders; it decides no result.
+__device__ __forceinline__ uint64_t morton_key(float x, float y, float z, const float* __restrict__ frame)
+{
+    const float qmax = (float)((1u << kMortonBits) - 1u);
+    const float v[3] = {x, y, z};
+    uint64_t code = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        float t = (v[a] - frame[a]) * frame[3 + a];
+        t = fminf(fmaxf(t, 0.f), qmax);
+        code |= spread3((uint32_t)t) << a;
+    }
+    return min(code, kLastKey - 1);
+}
+
+// ---- build: bounds ------------------------------------------------------------------------------------
+// Workgroup minimum and maximum per axis: thread a < 3 receives axis a's in (l, h).  (Indexing lo[] and hi[]
+// by the thread index instead would make the compiler move both arrays to LDS, 6 KiB a workgroup.)
+__device__ __forceinline__ void block_minmax(float (&lo)[3], float (&hi)[3], float (*s)[6], float& l, float& h)
+{
+    const int wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        lo[a] = wave_min(lo[a]);
+        hi[a] = wave_max(hi[a]);
+    }
+    if (lane_id() == 0)
+        for (int a = 0; a < 3; a++) {
+            s[wave][a] = lo[a];
+            s[wave][3 + a] = hi[a];
+        }
+    __syncthreads();
+    l = FLT_MAX, h = -FLT_MAX;
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        for (int w = 0; w < kWaves; w++) {
+            l = fminf(l, s[w][a]);
+            h = fmaxf(h, s[w][3 + a]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void nearest_bounds_kernel(const float* __restrict__ pts, long long P,
+                                                                float* __restrict__ partials)
+{
+    __shared__ float s[kWaves][6];
+    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock) {
+        const float v[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        if (!finite3(v[0], v[1], v[2])) continue;  // no candidate: it widens nothing
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            lo[a] = fminf(lo[a], v[a]);
+            hi[a] = fmaxf(hi[a], v[a]);
+        }
+    }
+    float l, h;
+    block_minmax(lo, hi, s, l, h);
+    if (threadIdx.x < 3) {
+        partials[blockIdx.x * 6 + threadIdx.x] = l;
+        partials[blockIdx.x * 6 + 3 + threadIdx.x] = h;
+    }
+}
+
+// frame = {lo.x, lo.y, lo.z, scale.x, scale.y, scale.z}
+__global__ __launch_bounds__(kBlock) void nearest_frame_kernel(const float* __restrict__ partials, int nparts,
+                                                               float* __restrict__ frame)
+{
+    __shared__ float s[kWaves][6];
+    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    for (int b = threadIdx.x; b < nparts; b += kBlock)
+        for (int a = 0; a < 3; a++) {
+            lo[a] = fminf(lo[a], partials[b * 6 + a]);
+            hi[a] = fmaxf(hi[a], partials[b * 6 + 3 + a]);
+        }
+    float l, h;
+    block_minmax(lo, hi, s, l, h);
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        const float ext = h - l;  // negative without a candidate
+        const float q = (float)((1u << kMortonBits) - 1u);
+        frame[a] = l;
+        frame[3 + a] = (ext > 0.f && ext < INFINITY) ? q / ext : 0.f;
+    }
+}
+
+// ---- build: keys, gather, boxes -----------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void nearest_point_keys_kernel(const float* __restrict__ pts, long long P,
+                                                                    const float* __restrict__ frame,
+                                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
+{
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= P) return;
+    const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    keys[i] = finite3(x, y, z) ? morton_key(x, y, z, frame) : kLastKey;
+    vals[i] = (uint32_t)i;
+}
+
+// Sorted point j = row order[j] as {x, y, z, bits(row)}.  Wave w of block b holds leaf 4b + w and writes its
+// box and first key.
+__global__ __launch_bounds__(kBlock) void nearest_gather_kernel(const float* __restrict__ pts, const uint32_t* __restrict__ order,
+                                                                const uint64_t* __restrict__ keys_sorted, long long P,
+                                                                float4* __restrict__ sp, long long nleaves,
+                                                                Box* __restrict__ leaves, uint64_t* __restrict__ leaf_keys)
+{
+    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const float nan = __uint_as_float(0x7fc00000u);
+    float4 p = make_float4(nan, nan, nan, 0.f);
+    bool valid = false;
+    if (j < P) {
+        const uint32_t i = order[j];
+        if (i < (uint32_t)P) {  // a permutation of [0, P) by construction
+            const float x = pts[3ll * i], y = pts[3ll * i + 1], z = pts[3ll * i + 2];
+            valid = finite3(x, y, z);
+            if (valid) p = make_float4(x, y, z, 0.f);
+            p.w = __uint_as_float(i);
+        }
+        sp[j] = p;
+    }
+    const long long L = j / kLeaf;  // wave-uniform
+    if (L >= nleaves) return;       // whole wave
+    const float lo[3] = {wave_min(valid ? p.x : FLT_MAX), wave_min(valid ? p.y : FLT_MAX), wave_min(valid ? p.z : FLT_MAX)};
+    const float hi[3] = {wave_max(valid ? p.x : -FLT_MAX), wave_max(valid ? p.y : -FLT_MAX), wave_max(valid ? p.z : -FLT_MAX)};
+    if (lane_id() == 0) {
+        leaves[L] = Box{make_float4(lo[0], lo[1], lo[2], 0.f), make_float4(hi[0], hi[1], hi[2], 0.f)};
+        leaf_keys[L] = keys_sorted[j];  // lane 0 of a leaf below nleaves: j < P
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void nearest_super_kernel(const Box* __restrict__ leaves, long long nleaves, int nsuper,
+                                                               Box* __restrict__ supers)
+{
+    const int S = blockIdx.x * kWaves + threadIdx.x / kWave;
+    if (S >= nsuper) return;
+    const long long l = (long long)S * kFan + lane_id();
+    const Box b = l < nleaves ? leaves[l]
+                              : Box{make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.f), make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.f)};
+    Box r;
+    r.lo = make_float4(wave_min(b.lo.x), wave_min(b.lo.y), wave_min(b.lo.z), 0.f);
+    r.hi = make_float4(wave_max(b.hi.x), wave_max(b.hi.y), wave_max(b.hi.z), 0.f);
+    if (lane_id() == 0) supers[S] = r;
+}
+
+// ---- query --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void nearest_query_keys_kernel(const float* __restrict__ queries, long long Q,
+                                                                    const float* __restrict__ frame,
+                                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
+{
+    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= Q) return;
+    keys[j] = morton_key(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], frame);
+    vals[j] = (uint32_t)j;
+}
+
+__global__ __launch_bounds__(kBlock) void nearest_none_kernel(long long Q, int32_t* __restrict__ idx_out,
+                                                              float* __restrict__ dist2_out)
+{
+    const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= Q) return;
+    idx_out[j] = -1;
+    dist2_out[j] = INFINITY;
+}
+
+struct IndexView {
+    const float* frame;
+    const float4* sp;
+    const Box* leaves;
+    const Box* supers;
+    const uint64_t* leaf_keys;
+    long long P, nleaves;
+    int nsuper;
+};
+
+// The last leaf whose first key is <= key (leaf 0 if none), by a 64-ary search: wave-uniform arguments and
+// result, every lane active.  The range at least halves per round.
+__device__ __forceinline__ long long find_leaf(const uint64_t* __restrict__ leaf_keys, long long nleaves, uint64_t key,
+                                               int lane)
+{
+    long long lo = 0, n = nleaves;
+    while (n > 1) {
+        const long long step = (n + kWave - 1) / kWave;
+        const long long i = lo + lane * step;
+        const bool le = i < lo + n && leaf_keys[i] <= key;
+        const int cnt = __popcll(__ballot(le));  // the keys ascend: lanes 0 .. cnt - 1
+        const long long nlo = lo + (long long)max(cnt - 1, 0) * step;
+        n = min(step, lo + n - nlo);
+        lo = nlo;
+    }
+    return lo;
+}
+
+// Appends the sorted position `s` of every lane with `flag` to the hard list (phase 2's input): one atomic per
+// wave.  A query is appended once at most, so the list holds at most Q entries.
+__device__ __forceinline__ void push_hard(bool flag, long long s, int lane, uint32_t* __restrict__ hard,
+                                          Counters* __restrict__ counters)
+{
+    const uint64_t m = __ballot(flag);
+    if (!m) return;
+    uint32_t at = 0;
+    if (lane == 0) at = atomicAdd(&counters->hard, (uint32_t)__popcll(m));
+    at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+    if (flag) hard[at + __popcll(m & lanes_below(lane))] = (uint32_t)s;
+}
+
+// best = min(best, candidate k) for the point held by lane k of `pt`, broadcast to every lane.
+__device__ __forceinline__ void eval_lane(float4 pt, int k, float4 q, uint64_t& best)
+{
+    const float4 c = make_float4(uniform_lane(pt.x, k), uniform_lane(pt.y, k), uniform_lane(pt.z, k), uniform_lane(pt.w, k));
+    best = min(best, pack(sqdist(q, c), c.w));
+}
+
+__device__ __forceinline__ void store_result(uint64_t best, long long j, int32_t* __restrict__ idx_out,
+                                             float* __restrict__ dist2_out)
+{
+    const uint32_t d = (uint32_t)(best >> 32);
+    const bool none = d > kInfBits;  // nothing found, or only NaN distances (non-candidate rows)
+    idx_out[j] = none ? -1 : (int32_t)(uint32_t)best;
+    dist2_out[j] = none ? INFINITY : __uint_as_float(d);
+}
+
+__global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
+                                                              const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
+                                                              int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
+                                                              uint32_t* __restrict__ hard, Counters* __restrict__ counters)
+{
+    __shared__ uint32_t s_list[kWaves][kListCap];
+    const int wave = threadIdx.x / kWave;
+    const int lane = lane_id();
+    const long long base = ((long long)blockIdx.x * kWaves + wave) * kWave;
+    if (base >= Q) return;  // whole wave; no workgroup barrier below
+
+    const long long s = base + lane;
+    long long j = 0;
+    bool inq = s < Q;
+    if (inq) {
+        j = qorder[s];
+        inq = j < Q;  // a permutation of [0, Q) by construction
+    }
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (inq) q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
+    const bool active = inq && finite3(q.x, q.y, q.z);
+    uint64_t best = ~0ull;
+    if (inq && !active) store_result(best, j, idx_out, dist2_out);
+    if (!__ballot(active)) return;
+
+    const long long P = ix.P, nleaves = ix.nleaves;
+    // A wave whose keys span many leaves (few queries against a large cloud) would seed, walk and then bail out:
+    // its queries go to phase 2 at once, which seeds each from its own leaf.
+    {
+        const long long lf = find_leaf(ix.leaf_keys, nleaves, qkeys[base], lane);
+        const long long ll = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave - 1, Q - 1)], lane);
+        if (ll - lf > kSpanBail) {
+            push_hard(active, s, lane, hard, counters);
+            return;
+        }
+    }
+    // seed: the leaf of the wave's median key and its two Morton neighbours, every point against every lane
+    const long long Ls = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave / 2, Q - 1)], lane);
+    for (long long C = max(Ls - 1, 0ll); C <= min(Ls + 1, nleaves - 1); C++) {
+        const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
+        const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
+#pragma unroll 16
+        for (int k = 0; k < kLeaf; k++)
+            if (k < nc) eval_lane(pt, k, q, best);  // wave-uniform
+    }
+
+    // the wave's query AABB and the largest lane bound: the coarse filter
+    const float4 qlo = make_float4(wave_min(active ? q.x : FLT_MAX), wave_min(active ? q.y : FLT_MAX),
+                                   wave_min(active ? q.z : FLT_MAX), 0.f);
+    const float4 qhi = make_float4(wave_max(active ? q.x : -FLT_MAX), wave_max(active ? q.y : -FLT_MAX),
+                                   wave_max(active ? q.z : -FLT_MAX), 0.f);
+    uint32_t ub = wave_max_u32(active ? bound_bits(best) : 0u);
+
+    uint32_t* list = s_list[wave];
+    int nlist = 0;
+    bool bail = false;
+    for (int s0 = 0; s0 < ix.nsuper && !bail; s0 += kWave) {  // one super-box per lane
+        const int sidx = s0 + lane;
+        bool pass = false;
+        if (sidx < ix.nsuper) pass = box_box_lb(ix.supers[sidx], qlo, qhi) <= ub;
+        uint64_t smask = __ballot(pass);
+        while (smask) {
+            const int S = s0 + __builtin_ctzll(smask);
+            smask &= smask - 1;
+            const long long l = (long long)S * kFan + lane;
+            bool lpass = false;
+            if (l < nleaves && (l < Ls - 1 || l > Ls + 1))  // those three were the seed
+                lpass = box_box_lb(ix.leaves[l], qlo, qhi) <= ub;
+            const uint64_t lm = __ballot(lpass);
+            const int cnt = __popcll(lm);
+            if (cnt == 0) continue;
+            if (nlist + cnt > kBailout) {
+                bail = true;
+                break;
+            }
+            if (lpass) list[nlist + __popcll(lm & lanes_below(lane))] = (uint32_t)l;
+            nlist += cnt;
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (bail) {
+        // The wave's queries are spread too far for one coarse filter (queries far outside the cloud, or on
+        // both sides of a Morton jump): phase 2 searches each with its own seed and bound.
+        push_hard(active, s, lane, hard, counters);
+        return;
+    }
+
+    for (int i = 0; i < nlist; i++) {
+        const long long C = (long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)list[i]);
+        const Box lb = ix.leaves[C];  // wave-uniform address
+        // fine filter: some lane's own bound reaches the leaf
+        if (!__ballot(active && box_point_lb(lb, q) <= bound_bits(best))) continue;
+        const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
+        const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
+        // a point is evaluated if it is a candidate within the largest lane bound of the query AABB
+        uint64_t pm = __ballot(lane < nc && pt.x == pt.x && box_point_lb(Box{qlo, qhi}, pt) <= ub);
+        while (pm) {
+            const int k = __builtin_ctzll(pm);
+            pm &= pm - 1;
+            eval_lane(pt, k, q, best);
+        }
+        ub = wave_max_u32(active ? bound_bits(best) : 0u);
+    }
+    if (active) store_result(best, j, idx_out, dist2_out);
+}
+
+// Phase 2: one wave per hard query; lane c holds candidate c of a leaf.
+__global__ __launch_bounds__(kBlock) void nearest_hard_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
+                                                              const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
+                                                              int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
+                                                              const uint32_t* __restrict__ hard, const Counters* __restrict__ counters)
+{
+    const int lane = lane_id();
+    const long long P = ix.P, nleaves = ix.nleaves;
+    const uint32_t nhard = min(counters->hard, (uint32_t)Q);
+    const uint32_t nw = gridDim.x * kWaves;
+    for (uint32_t h = blockIdx.x * kWaves + threadIdx.x / kWave; h < nhard; h += nw) {
+        const long long s = hard[h];
+        if (s >= Q) continue;  // written by phase 1: below Q by construction
+        const long long j = qorder[s];
+        if (j >= Q) continue;
+        const float4 q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
+        const long long L = find_leaf(ix.leaf_keys, nleaves, qkeys[s], lane);
+        uint64_t mine = ~0ull;
+        for (long long C = max(L - 1, 0ll); C <= min(L + 1, nleaves - 1); C++) {
+            const long long c = C * kLeaf + lane;
+            if (c < P) {
+                const float4 pt = ix.sp[c];
+                mine = min(mine, pack(sqdist(q, pt), pt.w));
+            }
+        }
+        uint64_t best = wave_min_u64(mine);
+        for (int s0 = 0; s0 < ix.nsuper; s0 += kWave) {  // one super-box per lane
+            const int sidx = s0 + lane;
+            bool pass = false;
+            if (sidx < ix.nsuper) pass = box_point_lb(ix.supers[sidx], q) <= bound_bits(best);
+            uint64_t smask = __ballot(pass);
+            while (smask) {
+                const int S = s0 + __builtin_ctzll(smask);
+                smask &= smask - 1;
+                const long long l = (long long)S * kFan + lane;
+                bool lpass = false;
+                if (l < nleaves && (l < L - 1 || l > L + 1)) lpass = box_point_lb(ix.leaves[l], q) <= bound_bits(best);
+                uint64_t lmask = __ballot(lpass);
+                if (!lmask) continue;
+                while (lmask) {
+                    const long long c = ((long long)S * kFan + __builtin_ctzll(lmask)) * kLeaf + lane;
+                    lmask &= lmask - 1;
+                    if (c < P) {
+                        const float4 pt = ix.sp[c];
+                        mine = min(mine, pack(sqdist(q, pt), pt.w));
+                    }
+                }
+                best = wave_min_u64(mine);
+            }
+        }
+        if (lane == 0) store_result(best, j, idx_out, dist2_out);
+    }
+}
+
+// ---- layouts ------------------------------------------------------------------------------------------
+struct IndexLayout {
+    float* frame;
+    float4* sp;
+    Box *leaves, *supers;
+    uint64_t* leaf_keys;
+    long long nleaves;
+    int nsuper;
+    size_t total;
+};
+
+IndexLayout index_layout(void* base, long long P)
+{
+    IndexLayout l;
+    l.nleaves = ceil_div(P, kLeaf);
+    l.nsuper = (int)ceil_div(l.nleaves, kFan);
+    Carver c(base);
+    l.frame = c.take<float>(8);
+    l.sp = c.take<float4>(P);
+    l.leaves = c.take<Box>(l.nleaves);
+    l.supers = c.take<Box>(l.nsuper);
+    l.leaf_keys = c.take<uint64_t>(l.nleaves);
+    l.total = c.used;
+    return l;
+}
+
+// Both calls sort n (key, row) pairs.
+struct SortLayout {
+    uint64_t *keys, *keys_sorted;
+    uint32_t *vals, *vals_sorted;
+    void* sort_tmp;
+    size_t sort_bytes;
+};
+
+void sort_layout(Carver& c, long long n, SortLayout& l)
+{
+    l.keys = c.take<uint64_t>(n);
+    l.keys_sorted = c.take<uint64_t>(n);
+    l.vals = c.take<uint32_t>(n);
+    l.vals_sorted = c.take<uint32_t>(n);
+    l.sort_bytes = sort_u64_scratch(n);
+    l.sort_tmp = c.take<char>(l.sort_bytes);
+}
+
+struct BuildLayout {
+    SortLayout sort;
+    float* partials;
+    size_t total;
+};
+
+BuildLayout build_layout(void* base, long long P)
+{
+    BuildLayout l;
+    Carver c(base);
+    sort_layout(c, P, l.sort);
+    l.partials = c.take<float>(kBoundBlocks * 6);
+    l.total = c.used;
+    return l;
+}
+
+struct QueryLayout {
+    Counters* counters;  // first: the header documents the word
+    SortLayout sort;
+    uint32_t* hard;
+    size_t total;
+};
+
+QueryLayout query_layout(void* base, long long Q)
+{
+    QueryLayout l;
+    Carver c(base);
+    l.counters = c.take<Counters>(1);
+    sort_layout(c, Q, l.sort);
+    l.hard = c.take<uint32_t>(Q);
+    l.total = c.used;
+    return l;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+bool overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return a && b && na && nb && pa < pb + nb && pb < pa + na;
+}
+
+bool in_range(long long n) { return n >= 0 && n <= kNearestMax; }
+
+}  // namespace
+}  // namespace hidegs
+
+extern "C" size_t hidegs_nearest_index_bytes(long long P)
+{
+    return P > 0 && hidegs::in_range(P) ? hidegs::index_layout(nullptr, P).total : 0;
+}
+
+extern "C" size_t hidegs_nearest_build_scratch_bytes(long long P)
+{
+    return P > 0 && hidegs::in_range(P) ? hidegs::build_layout(nullptr, P).total : 0;
+}
+
+extern "C" size_t hidegs_nearest_query_scratch_bytes(long long P, long long Q)
+{
+    return Q > 0 && hidegs::in_range(Q) && hidegs::in_range(P) ? hidegs::query_layout(nullptr, Q).total : 0;
+}
+
+extern "C" int hidegs_nearest_build(void* index, size_t index_bytes, void* scratch, size_t scratch_bytes,
+                                    const float* points, long long P, void* stream)
+{
+    using namespace hidegs;
+    hipStream_t s = as_stream(stream);
+    if (int rc = take_async_error("hidegs_nearest_build", s)) return rc;
+    if (!in_range(P)) return fail(HIDEGS_E_ARG, "nearest_build: P must be in [0, 2^31)");
+    if (P == 0) return 0;
+    if (!points) return fail(HIDEGS_E_ARG, "nearest_build: NULL points");
+    if (!index || !aligned16(index) || index_bytes < index_layout(nullptr, P).total)
+        return fail(HIDEGS_E_ARG, "nearest_build: index buffer NULL, not 16-byte aligned or too small");
+    if (!scratch || !aligned16(scratch) || scratch_bytes < build_layout(nullptr, P).total)
+        return fail(HIDEGS_E_ARG, "nearest_build: scratch buffer NULL, not 16-byte aligned or too small");
+    if (overlap(index, index_bytes, points, (size_t)P * 12) || overlap(index, index_bytes, scratch, scratch_bytes))
+        return fail(HIDEGS_E_ARG, "nearest_build: index overlaps points or scratch");
+    const IndexLayout ix = index_layout(index, P);
+    const BuildLayout b = build_layout(scratch, P);
+    const int nb = (int)ceil_div(P, kBlock);
+    const int nbound = std::min(kBoundBlocks, nb);
+    HIDEGS_LAUNCH("nearest_bounds", nearest_bounds_kernel, dim3(nbound), dim3(kBlock), 0, s, points, P, b.partials);
+    HIDEGS_LAUNCH("nearest_frame", nearest_frame_kernel, dim3(1), dim3(kBlock), 0, s, b.partials, nbound, ix.frame);
+    HIDEGS_LAUNCH("nearest_point_keys", nearest_point_keys_kernel, dim3(nb), dim3(kBlock), 0, s, points, P, ix.frame,
+                  b.sort.keys, b.sort.vals);
+    if (int rc = sort_pairs_u64(b.sort.sort_tmp, b.sort.sort_bytes, b.sort.keys, b.sort.keys_sorted, b.sort.vals,
+                                b.sort.vals_sorted, P, 0, 3 * kMortonBits, s))
+        return rc;
+    HIDEGS_LAUNCH("nearest_gather", nearest_gather_kernel, dim3(nb), dim3(kBlock), 0, s, points, b.sort.vals_sorted,
+                  b.sort.keys_sorted, P, ix.sp, ix.nleaves, ix.leaves, ix.leaf_keys);
+    HIDEGS_LAUNCH("nearest_super", nearest_super_kernel, dim3((unsigned)ceil_div(ix.nsuper, kWaves)), dim3(kBlock), 0, s,
+                  ix.leaves, ix.nleaves, ix.nsuper, ix.supers);
+    return check_launch("nearest_build", s, 0);
+}
+
+extern "C" int hidegs_nearest_query(const void* index, size_t index_bytes, long long P, void* scratch,
+                                    size_t scratch_bytes, const float* queries, long long Q, int32_t* idx_out,
+                                    float* dist2_out, void* stream)
+{
+    using namespace hidegs;
+    hipStream_t s = as_stream(stream);
+    if (int rc = take_async_error("hidegs_nearest_query", s)) return rc;
+    if (!in_range(P)) return fail(HIDEGS_E_ARG, "nearest_query: P must be in [0, 2^31)");
+    if (!in_range(Q)) return fail(HIDEGS_E_ARG, "nearest_query: Q must be in [0, 2^31)");
+    if (Q == 0) return 0;
+    if (!queries) return fail(HIDEGS_E_ARG, "nearest_query: NULL queries");
+    if (!idx_out) return fail(HIDEGS_E_ARG, "nearest_query: NULL idx_out");
+    if (!dist2_out) return fail(HIDEGS_E_ARG, "nearest_query: NULL dist2_out");
+    if (P > 0) {
+        if (!index || !aligned16(index) || index_bytes < index_layout(nullptr, P).total)
+            return fail(HIDEGS_E_ARG, "nearest_query: index buffer NULL, not 16-byte aligned or too small for P");
+        if (!scratch || !aligned16(scratch) || scratch_bytes < query_layout(nullptr, Q).total)
+            return fail(HIDEGS_E_ARG, "nearest_query: scratch buffer NULL, not 16-byte aligned or too small");
+    } else {
+        index = nullptr, index_bytes = 0, scratch = nullptr, scratch_bytes = 0;  // not used
+    }
+    const size_t out_bytes = (size_t)Q * 4;
+    struct {
+        const void* p;
+        size_t n;
+        const char* name;
+    } const inputs[] = {{queries, (size_t)Q * 12, "queries"}, {index, index_bytes, "the index"}, {scratch, scratch_bytes, "scratch"}};
+    for (const auto& in : inputs) {
+        if (overlap(idx_out, out_bytes, in.p, in.n))
+            return fail(HIDEGS_E_ARG, std::string("nearest_query: idx_out overlaps ") + in.name);
+        if (overlap(dist2_out, out_bytes, in.p, in.n))
+            return fail(HIDEGS_E_ARG, std::string("nearest_query: dist2_out overlaps ") + in.name);
+    }
+    if (overlap(idx_out, out_bytes, dist2_out, out_bytes)) return fail(HIDEGS_E_ARG, "nearest_query: dist2_out overlaps idx_out");
+    const unsigned nb = (unsigned)ceil_div(Q, kBlock);
+    if (P == 0) {
+        HIDEGS_LAUNCH("nearest_none", nearest_none_kernel, dim3(nb), dim3(kBlock), 0, s, Q, idx_out, dist2_out);
+        return check_launch("nearest_query", s, 0);
+    }
+    const IndexLayout il = index_layout(const_cast<void*>(index), P);
+    const IndexView ix{il.frame, il.sp, il.leaves, il.supers, il.leaf_keys, P, il.nleaves, il.nsuper};
+    const QueryLayout l = query_layout(scratch, Q);
+    if (hipMemsetAsync(l.counters, 0, sizeof(Counters), s) != hipSuccess)
+        return fail(HIDEGS_E_HIP, "nearest_query: clearing the counter failed");
+    HIDEGS_LAUNCH("nearest_query_keys", nearest_query_keys_kernel, dim3(nb), dim3(kBlock), 0, s, queries, Q, ix.frame,
+                  l.sort.keys, l.sort.vals);
+    if (int rc = sort_pairs_u64(l.sort.sort_tmp, l.sort.sort_bytes, l.sort.keys, l.sort.keys_sorted, l.sort.vals,
+                                l.sort.vals_sorted, Q, 0, 3 * kMortonBits, s))
+        return rc;
+    const unsigned nwg = (unsigned)ceil_div(Q, kBlock);  // one wave per 64 sorted queries
+    HIDEGS_LAUNCH("nearest_wave", nearest_wave_kernel, dim3(nwg), dim3(kBlock), 0, s, ix, queries, Q, l.sort.keys_sorted,
+                  l.sort.vals_sorted, idx_out, dist2_out, l.hard, l.counters);
+    HIDEGS_LAUNCH("nearest_hard", nearest_hard_kernel, dim3(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves))),
+                  dim3(kBlock), 0, s, ix, queries, Q, l.sort.keys_sorted, l.sort.vals_sorted, idx_out, dist2_out, l.hard,
+                  l.counters);
+    return check_launch("nearest_query", s, 0);
+}

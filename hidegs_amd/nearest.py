@@ -1,0 +1,117 @@
+"""Nearest-point index (include/hidegs_nearest.h, csrc/nearest.hip): built once over a point cloud on the GPU,
+then asked for the nearest point of arbitrary positions -- exactly, lowest row index among equals.
+
+    index = NearestIndex(points)        # (P, 3) contiguous float32 GPU tensor; builds on the current stream
+    idx, d2 = index.query(queries)      # (Q,) int32 (-1: none), (Q,) float32 squared distances
+    idx, d2 = nearest(points, queries)  # build + query
+
+The index holds its own copy of the points: rebuild it after the positions move or the rows are resized.
+"""
+from __future__ import annotations
+
+from typing import Tuple
+
+import torch
+
+from . import _lib
+
+_MAX = (1 << 31) - 1
+
+
+def _need_rows(t, what: str) -> int:
+    """`t` is a contiguous (n, 3) float32 tensor; returns n."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"nearest: {what} is not a tensor")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+        raise RuntimeError(f"nearest: {what}: expected a contiguous (n, 3) float32 tensor, got {t.dtype} of shape "
+                           f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    if t.shape[0] > _MAX:
+        raise RuntimeError(f"nearest: {what}: at most 2^31 - 1 rows")
+    return t.shape[0]
+
+
+def _need_gpu(dev: torch.device, **tensors) -> None:
+    for what, t in tensors.items():
+        if t.device.type != "cuda":
+            raise RuntimeError(f"nearest: {what}: expected a GPU tensor, got one on {t.device}")
+        if dev is not None and t.device != dev:
+            raise RuntimeError(f"nearest: tensors on different devices: the index on {dev}, {what} on {t.device}")
+
+
+def _size_class(q: int) -> int:
+    """The power of two at or above q, 1024 at least and 2^31 - 1 at most (the largest Q there is): one scratch
+    tensor serves every size of its class."""
+    return min(max(1024, 1 << (q - 1).bit_length()), _MAX)
+
+
+class NearestIndex:
+    """An index over `points`, a contiguous (P, 3) float32 GPU tensor, built on the current stream.
+
+    A row with a NaN or infinite coordinate is never returned.  The index buffer (`self.index`, a uint8 tensor)
+    is self-contained: `points` may change afterwards, and the index then still answers for the old positions.
+    Queries only read it, so it may be queried from several streams at once; the scratch tensors are kept per
+    stream and query size class, so repeated queries allocate nothing.
+    """
+
+    def __init__(self, points: torch.Tensor):
+        self.P = _need_rows(points, "points")
+        if self.P:
+            _lib.device_of(points)
+        _need_gpu(None, points=points)
+        self.device = points.device
+        self._scratch = {}
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            self.index = torch.empty(L.hidegs_nearest_index_bytes(self.P), dtype=torch.uint8, device=self.device)
+            if self.P == 0:
+                return
+            tmp = torch.empty(L.hidegs_nearest_build_scratch_bytes(self.P), dtype=torch.uint8, device=self.device)
+            rc = L.hidegs_nearest_build(self.index.data_ptr(), self.index.numel(), tmp.data_ptr(), tmp.numel(),
+                                        points.data_ptr(), self.P, _lib.stream_handle(self.device))
+            _lib.check(rc, "nearest_build")
+
+    def query(self, queries: torch.Tensor, out: Tuple[torch.Tensor, torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(idx, d2) of `queries`, a contiguous (Q, 3) float32 tensor on the index's device: idx (Q,) int32, the
+        row of the nearest point (the lowest such row among equal distances; -1 where the query has a NaN or
+        infinite coordinate or the cloud has no finite row), and d2 (Q,) float32, its squared distance (+inf
+        with -1).  out=(idx, d2) reuses two such tensors.  Runs on the current stream; no host synchronisation."""
+        Q = _need_rows(queries, "queries")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise RuntimeError("nearest: out must be a pair (idx, d2)")
+            for what, t, dtype in (("out idx", out[0], torch.int32), ("out d2", out[1], torch.float32)):
+                if not isinstance(t, torch.Tensor):
+                    raise RuntimeError(f"nearest: {what} is not a tensor")
+                if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+                    raise RuntimeError(f"nearest: {what}: expected a contiguous 1-D {dtype} tensor, got {t.dtype} of "
+                                       f"shape {tuple(t.shape)}")
+                if t.numel() != Q:
+                    raise RuntimeError(f"nearest: {what} has {t.numel()} entries, queries has {Q} rows")
+        if Q:
+            _lib.device_of(queries, *(out or ()))
+        _need_gpu(self.device, queries=queries, **({} if out is None else {"out idx": out[0], "out d2": out[1]}))
+        with torch.cuda.device(self.device):
+            idx, d2 = out if out is not None else (torch.empty(Q, dtype=torch.int32, device=self.device),
+                                                   torch.empty(Q, dtype=torch.float32, device=self.device))
+            if Q == 0:
+                return idx, d2
+            L = _lib.lib()
+            stream = _lib.stream_handle(self.device)
+            tmp = None
+            if self.P:
+                key = (stream, _size_class(Q))
+                tmp = self._scratch.get(key)
+                if tmp is None:
+                    tmp = self._scratch[key] = torch.empty(L.hidegs_nearest_query_scratch_bytes(self.P, key[1]),
+                                                           dtype=torch.uint8, device=self.device)
+            rc = L.hidegs_nearest_query(_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp),
+                                        0 if tmp is None else tmp.numel(), queries.data_ptr(), Q, idx.data_ptr(),
+                                        d2.data_ptr(), stream)
+            _lib.check(rc, "nearest_query")
+        return idx, d2
+
+
+def nearest(points: torch.Tensor, queries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """NearestIndex(points).query(queries): for one set of queries against a cloud that will change."""
+    return NearestIndex(points).query(queries)

@@ -1,0 +1,136 @@
+"""Oracles of the nearest-point index (include/hidegs_nearest.h).  Test infrastructure, no test here.
+
+brute():  float64 squared distances from every query to *all* points, by torch on the given device.
+check():  every output of the kernel against brute(), with bounds derived from the fp32 expression.
+exact():  the bit-exact answer, in numpy, for inputs whose fp32 arithmetic is exact (small integers and
+          half-integers): there every evaluation order and contraction gives the same bits.
+exact_on(): the same by torch on a device, for query sets too large for numpy's brute force.
+"""
+import numpy as np
+import torch
+
+# The contract's distance fmaf(dz, dz, fmaf(dx, dx, dy * dy)) carries, with u = 2^-24, at most 5u of relative
+# error: 2u from the rounded difference (squared) and one rounding for each of the product and the two fmaf.
+# The kernel's winner can therefore exceed the true minimum by at most (1 + 5u) / (1 - 5u) - 1 < 16u = 2^-20,
+# and its reported distance is within 8u = 2^-21 of the float64 value (while the squared terms are normal).
+WINNER_SLACK = 2.0 ** -20
+DIST_SLACK = 2.0 ** -21
+
+
+def _f64(a, device):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=device, dtype=torch.float64).reshape(-1, 3)
+
+
+def brute(points, queries, device="cpu"):
+    """(Dmin, amin, none): per query the float64 minimum over the candidate points (rows with three finite
+    coordinates) of the squared distance, the lowest row that attains it (int64), and whether the contract
+    returns nothing (a non-finite query, or no candidate): then Dmin = +inf and amin = -1."""
+    p, q = _f64(points, device), _f64(queries, device)
+    P, Q = p.shape[0], q.shape[0]
+    cand = torch.isfinite(p).all(1)
+    qfin = torch.isfinite(q).all(1)
+    dmin = torch.full((Q,), float("inf"), dtype=torch.float64, device=device)
+    amin = torch.full((Q,), -1, dtype=torch.int64, device=device)
+    none = ~qfin if bool(cand.any()) else torch.ones_like(qfin)
+    if P == 0 or Q == 0 or not bool(cand.any()):
+        return dmin, amin, none
+    pc = torch.where(cand[:, None], p, torch.zeros_like(p))
+    rows = torch.arange(P, dtype=torch.int64, device=device)
+    chunk = max(1, min(Q, 40_000_000 // P))  # chunk x P x (8 + 8 + 8) bytes at a time
+    for a in range(0, Q, chunk):
+        qq = torch.where(qfin[a:a + chunk, None], q[a:a + chunk], torch.zeros_like(q[a:a + chunk]))
+        D = (pc[None, :, 0] - qq[:, None, 0]) ** 2
+        D += (pc[None, :, 1] - qq[:, None, 1]) ** 2
+        D += (pc[None, :, 2] - qq[:, None, 2]) ** 2
+        D[:, ~cand] = float("inf")
+        m = D.min(1).values
+        first = torch.where(D == m[:, None], rows[None, :], P).min(1).values
+        dmin[a:a + chunk] = m
+        amin[a:a + chunk] = first
+    dmin[none] = float("inf")
+    amin[none] = -1
+    return dmin, amin, none
+
+
+def check(points, queries, idx, d2, device="cpu", oracle=None):
+    """Asserts the contract's bounds for every query (no exclusions, no sampling) and returns how many indices
+    differ from the float64 argmin (a figure to print, not a gate).  oracle: a brute() result to reuse."""
+    p, q = _f64(points, device), _f64(queries, device)
+    P, Q = p.shape[0], q.shape[0]
+    idx = torch.as_tensor(idx).to(device)
+    d2 = torch.as_tensor(d2).to(device)
+    assert idx.shape == (Q,) and d2.shape == (Q,) and idx.dtype == torch.int32 and d2.dtype == torch.float32
+    dmin, amin, none = brute(points, queries, device) if oracle is None else oracle
+    assert bool((idx[none] == -1).all()), "a query without an answer did not receive -1"
+    assert bool((d2[none] == float("inf")).all()), "a query without an answer did not receive +inf"
+    got = idx[~none].long()
+    assert bool(((got >= 0) & (got < P)).all()), "an index out of range (or -1 where an answer exists)"
+    diff = p[got] - q[~none]
+    at = (diff * diff).sum(1)  # float64 distance to the returned row; inf or NaN for a non-candidate row
+    lim = dmin[~none] * (1.0 + WINNER_SLACK)
+    bad = ~(at <= lim)
+    assert not bool(bad.any()), (f"{int(bad.sum())} queries: the returned row is not nearest, first query "
+                                 f"{int(torch.nonzero(~none)[bad][0])}: {float(at[bad][0])} > {float(dmin[~none][bad][0])}")
+    err = (d2[~none].double() - at).abs()
+    bad = ~(err <= DIST_SLACK * at)
+    assert not bool(bad.any()), f"{int(bad.sum())} queries: the reported distance is off by more than 2^-21"
+    return int((got != amin[~none]).sum())
+
+
+def exact_on(points, queries, device):
+    """exact() by torch on `device`: (idx int32, d2 float32) as numpy arrays.  The same rule -- the minimum of
+    bits(d) << 32 | row over the rows, a NaN distance (a non-candidate row) above +inf -- on fp32 arithmetic
+    that is exact for the inputs this is meant for, so that the device's own evaluation order changes nothing."""
+    p = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)).to(device)
+    q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 3)).to(device)
+    P, Q = p.shape[0], q.shape[0]
+    idx = torch.full((Q,), -1, dtype=torch.int32, device=device)
+    d2 = torch.full((Q,), float("inf"), dtype=torch.float32, device=device)
+    if P == 0 or Q == 0:
+        return idx.cpu().numpy(), d2.cpu().numpy()
+    p = torch.where(torch.isfinite(p).all(1)[:, None], p, torch.full_like(p, float("nan")))
+    rows = torch.arange(P, dtype=torch.int64, device=device)
+    nan_hi = torch.tensor(0x7FC00000, dtype=torch.int64, device=device)
+    chunk = max(1, 30_000_000 // P)
+    for a in range(0, Q, chunk):
+        qq = q[a:a + chunk]
+        dx = p[None, :, 0] - qq[:, None, 0]
+        dy = p[None, :, 1] - qq[:, None, 1]
+        dz = p[None, :, 2] - qq[:, None, 2]
+        d = dz * dz + (dx * dx + dy * dy)
+        hi = torch.where(torch.isnan(d), nan_hi, d.view(torch.int32).to(torch.int64))  # d >= 0: the bits ascend
+        best = ((hi << 32) | rows[None, :]).min(1).values
+        ok = ((best >> 32) <= 0x7F800000) & torch.isfinite(qq).all(1)
+        idx[a:a + chunk] = torch.where(ok, best & 0xFFFFFFFF, -1).to(torch.int32)
+        d2[a:a + chunk] = torch.where(ok, (best >> 32).to(torch.int32).view(torch.float32), float("inf"))
+    return idx.cpu().numpy(), d2.cpu().numpy()
+
+
+def exact(points, queries):
+    """(idx int32, d2 float32) by the contract's rule -- the candidate minimising (bits(d), row) -- in numpy fp32.
+    Only for inputs whose differences, squares and sums are exact in fp32."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 3)
+    P, Q = len(p), len(q)
+    idx = np.full(Q, -1, dtype=np.int32)
+    d2 = np.full(Q, np.inf, dtype=np.float32)
+    if P == 0 or Q == 0:
+        return idx, d2
+    rows = np.arange(P, dtype=np.uint64)
+    pnan = np.where(np.isfinite(p).all(1)[:, None], p, np.float32(np.nan))  # a non-candidate: NaN distance
+    chunk = max(1, 8_000_000 // P)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for a in range(0, Q, chunk):
+            qq = q[a:a + chunk]
+            dx = pnan[None, :, 0] - qq[:, None, 0]
+            dy = pnan[None, :, 1] - qq[:, None, 1]
+            dz = pnan[None, :, 2] - qq[:, None, 2]
+            d = dz * dz + (dx * dx + dy * dy)
+            key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | rows[None, :]
+            best = key.min(1)
+            hi = (best >> np.uint64(32)).astype(np.uint32)
+            ok = (hi <= 0x7F800000) & np.isfinite(qq).all(1)
+            idx[a:a + chunk] = np.where(ok, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
+            d2[a:a + chunk] = np.where(ok, hi.view(np.float32), np.float32(np.inf))
+    return idx, d2

@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in include/hidegs.h, include/hidegs_rows.h, include/hidegs_resize.h,
-include/hidegs_clone.h, include/hidegs_topk.h and include/hidegs_nearest.h (hidegs_amd/libhidegs.so).
+include/hidegs_clone.h, include/hidegs_topk.h, include/hidegs_nearest.h and include/hidegs_nearest_k.h
+(hidegs_amd/libhidegs.so).
 
 This is the only place that loads the native library.  It fails loudly: a missing
 library raises ImportError-like RuntimeError at first use, and a non-zero return
@@ -135,20 +136,26 @@ NEAREST_SIGNATURES = {
     "hidegs_nearest_query": (I, [P, SZ, LL, P, SZ, P, LL, P, P, P]),
 }
 
+# include/hidegs_nearest_k.h, in its order
+NEAREST_K_SIGNATURES = {
+    "hidegs_nearest_query_k_scratch_bytes": (SZ, [LL, LL, I]),
+    "hidegs_nearest_query_k": (I, [P, SZ, LL, P, SZ, P, LL, I, P, P, P, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
 
 def load_library(path: str) -> C.CDLL:
     """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h, hidegs_resize.h,
-    hidegs_clone.h, hidegs_topk.h and hidegs_nearest.h bound (lib() for the product build; tests load the
-    build.VARIANTS this way)."""
+    hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h and hidegs_nearest_k.h bound (lib() for the product build;
+    tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
                            "(or __graft_entry__.build()) to compile it for gfx950")
     dll = C.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES, **CLONE_SIGNATURES,
-                              **TOPK_SIGNATURES, **NEAREST_SIGNATURES}.items():
+                              **TOPK_SIGNATURES, **NEAREST_SIGNATURES, **NEAREST_K_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

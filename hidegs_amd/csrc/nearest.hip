@@ -36,6 +36,7 @@
 #include <string>
 
 #include "../../include/hidegs_nearest.h"
+#include "../../include/hidegs_nearest_k.h"
 #include "common.h"
 
 namespace hidegs {
@@ -602,6 +603,8 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb)
 
 bool in_range(long long n) { return n >= 0 && n <= kNearestMax; }
 
+#include "nearest_k.h"
+
 }  // namespace
 }  // namespace hidegs
 
@@ -709,4 +712,16 @@ extern "C" int hidegs_nearest_query(const void* index, size_t index_bytes, long 
                   dim3(kBlock), 0, s, ix, queries, Q, l.sort.keys_sorted, l.sort.vals_sorted, idx_out, dist2_out, l.hard,
                   l.counters);
     return check_launch("nearest_query", s, 0);
+}
+
+extern "C" size_t hidegs_nearest_query_k_scratch_bytes(long long P, long long Q, int k)
+{
+    return hidegs::query_k_scratch_bytes(P, Q, k);
+}
+
+extern "C" int hidegs_nearest_query_k(const void* index, size_t index_bytes, long long P, void* scratch, size_t scratch_bytes,
+                                      const float* queries, long long Q, int k, const int32_t* exclude, int32_t* idx_out,
+                                      float* dist2_out, void* stream)
+{
+    return hidegs::query_k(index, index_bytes, P, scratch, scratch_bytes, queries, Q, k, exclude, idx_out, dist2_out, stream);
 }

@@ -1,14 +1,18 @@
-"""Nearest-point index (include/hidegs_nearest.h, csrc/nearest.hip): built once over a point cloud on the GPU,
-then asked for the nearest point of arbitrary positions -- exactly, lowest row index among equals.
+"""Nearest-point index (include/hidegs_nearest.h, include/hidegs_nearest_k.h, csrc/nearest.hip): built once over a
+point cloud on the GPU, then asked for the nearest point, or the k nearest, of arbitrary positions -- exactly,
+lowest row index among equals.
 
     index = NearestIndex(points)        # (P, 3) contiguous float32 GPU tensor; builds on the current stream
     idx, d2 = index.query(queries)      # (Q,) int32 (-1: none), (Q,) float32 squared distances
+    idx, d2 = index.query_k(queries, k, exclude=None)   # (Q, k) each, nearest first; exclude: a row per query
     idx, d2 = nearest(points, queries)  # build + query
+    idx, d2 = nearest_k(points, queries, k, exclude=None)
 
 The index holds its own copy of the points: rebuild it after the positions move or the rows are resized.
 """
 from __future__ import annotations
 
+import numbers
 from typing import Tuple
 
 import torch
@@ -16,6 +20,7 @@ import torch
 from . import _lib
 
 _MAX = (1 << 31) - 1
+K_MAX = 64  # of query_k
 
 
 def _need_rows(t, what: str) -> int:
@@ -111,7 +116,73 @@ class NearestIndex:
             _lib.check(rc, "nearest_query")
         return idx, d2
 
+    def query_k(self, queries: torch.Tensor, k: int, exclude: torch.Tensor = None,
+                out: Tuple[torch.Tensor, torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(idx, d2) of the k nearest rows of every query, 1 <= k <= 64: idx (Q, k) int32 and d2 (Q, k) float32,
+        ascending by (distance, row).  exclude: a contiguous (Q,) int32 tensor on the index's device; query j
+        never receives row exclude[j] (a value outside [0, P) excludes nothing) -- with exclude = arange(P)
+        and the cloud's own points as queries, every point's neighbours without itself.  Slots past the number
+        of candidates, and every slot of a query with a NaN or infinite coordinate, hold -1 and +inf.
+        out=(idx, d2) reuses two such tensors.  Runs on the current stream; no host synchronisation."""
+        Q = _need_rows(queries, "queries")
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise RuntimeError(f"nearest: k must be an integer, got {type(k).__name__}")
+        k = int(k)
+        if not 1 <= k <= K_MAX:
+            raise RuntimeError(f"nearest: k must be in [1, {K_MAX}], got {k}")
+        if exclude is not None:
+            if not isinstance(exclude, torch.Tensor):
+                raise RuntimeError("nearest: exclude is not a tensor")
+            if exclude.dtype != torch.int32 or exclude.dim() != 1 or not exclude.is_contiguous():
+                raise RuntimeError(f"nearest: exclude: expected a contiguous 1-D int32 tensor, got {exclude.dtype} of "
+                                   f"shape {tuple(exclude.shape)}")
+            if exclude.numel() != Q:
+                raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise RuntimeError("nearest: out must be a pair (idx, d2)")
+            for what, t, dtype in (("out idx", out[0], torch.int32), ("out d2", out[1], torch.float32)):
+                if not isinstance(t, torch.Tensor):
+                    raise RuntimeError(f"nearest: {what} is not a tensor")
+                if t.dtype != dtype or tuple(t.shape) != (Q, k) or not t.is_contiguous():
+                    raise RuntimeError(f"nearest: {what}: expected a contiguous ({Q}, {k}) {dtype} tensor, got "
+                                       f"{t.dtype} of shape {tuple(t.shape)}")
+        tensors = {"queries": queries}
+        if exclude is not None:
+            tensors["exclude"] = exclude
+        if out is not None:
+            tensors.update({"out idx": out[0], "out d2": out[1]})
+        if Q:
+            _lib.device_of(*tensors.values())
+        _need_gpu(self.device, **tensors)
+        with torch.cuda.device(self.device):
+            idx, d2 = out if out is not None else (torch.empty((Q, k), dtype=torch.int32, device=self.device),
+                                                   torch.empty((Q, k), dtype=torch.float32, device=self.device))
+            if Q == 0:
+                return idx, d2
+            L = _lib.lib()
+            stream = _lib.stream_handle(self.device)
+            tmp = None
+            if self.P:
+                # query's scratch tensors serve: the layout is the same, whatever k is
+                key = (stream, _size_class(Q))
+                need = L.hidegs_nearest_query_k_scratch_bytes(self.P, key[1], k)
+                tmp = self._scratch.get(key)
+                if tmp is None or tmp.numel() < need:
+                    tmp = self._scratch[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            rc = L.hidegs_nearest_query_k(_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp),
+                                          0 if tmp is None else tmp.numel(), queries.data_ptr(), Q, k,
+                                          _lib.ptr(exclude), idx.data_ptr(), d2.data_ptr(), stream)
+            _lib.check(rc, "nearest_query_k")
+        return idx, d2
+
 
 def nearest(points: torch.Tensor, queries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """NearestIndex(points).query(queries): for one set of queries against a cloud that will change."""
     return NearestIndex(points).query(queries)
+
+
+def nearest_k(points: torch.Tensor, queries: torch.Tensor, k: int, exclude: torch.Tensor = None
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """NearestIndex(points).query_k(queries, k, exclude)."""
+    return NearestIndex(points).query_k(queries, k, exclude)

@@ -142,20 +142,27 @@ NEAREST_K_SIGNATURES = {
     "hidegs_nearest_query_k": (I, [P, SZ, LL, P, SZ, P, LL, I, P, P, P, P]),
 }
 
+# include/hidegs_nearest_within.h, in its order
+NEAREST_WITHIN_SIGNATURES = {
+    "hidegs_nearest_query_within_scratch_bytes": (SZ, [LL, LL, I]),
+    "hidegs_nearest_query_within": (I, [P, SZ, LL, P, SZ, P, LL, P, I, I, P, P, P, P, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
 
 def load_library(path: str) -> C.CDLL:
     """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h, hidegs_resize.h,
-    hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h and hidegs_nearest_k.h bound (lib() for the product build;
+    hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h and hidegs_nearest_within.h bound (lib() for the product build;
     tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
                            "(or __graft_entry__.build()) to compile it for gfx950")
     dll = C.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES, **CLONE_SIGNATURES,
-                              **TOPK_SIGNATURES, **NEAREST_SIGNATURES, **NEAREST_K_SIGNATURES}.items():
+                              **TOPK_SIGNATURES, **NEAREST_SIGNATURES, **NEAREST_K_SIGNATURES,
+                              **NEAREST_WITHIN_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,5 @@
 """Build recipe for hidegs_amd/libhidegs.so (the C-ABI library of include/hidegs.h, hidegs_rows.h,
-hidegs_resize.h, hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h and hidegs_nearest_k.h).
+hidegs_resize.h, hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h and hidegs_nearest_within.h).
 
 Built in-tree with hipcc for gfx950 so the .so travels to the GPU box with the
 repository snapshot.  `python -m hidegs_amd.build` or `__graft_entry__.build()`.
@@ -36,7 +36,8 @@ HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, 
                                                          os.path.join(INCLUDE, "hidegs_clone.h"),
                                                          os.path.join(INCLUDE, "hidegs_topk.h"),
                                                          os.path.join(INCLUDE, "hidegs_nearest.h"),
-                                                         os.path.join(INCLUDE, "hidegs_nearest_k.h")]
+                                                         os.path.join(INCLUDE, "hidegs_nearest_k.h"),
+                                                         os.path.join(INCLUDE, "hidegs_nearest_within.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf, so the
 # oracle (oracle/knn_ref.c) can reproduce each rounding step bit for bit.

@@ -29,6 +29,10 @@
 // distance of every query it is skipped for -- an equal bound may hide an equal distance at a lower row.
 // Seeds, ordering and the bail-out change the speed only.  All distances and bounds are non-negative
 // floats (or +inf), so they are compared as unsigned integers.
+//
+// Two further queries on the same index are stages of this file, included below inside its namespace: the k
+// nearest (nearest_k.h) and the count and the k nearest within a radius (nearest_within.h).  Neither adds to
+// the build or to the scratch layout.
 #include <float.h>
 #include <stdint.h>
 
@@ -37,6 +41,7 @@
 
 #include "../../include/hidegs_nearest.h"
 #include "../../include/hidegs_nearest_k.h"
+#include "../../include/hidegs_nearest_within.h"
 #include "common.h"
 
 namespace hidegs {
@@ -604,6 +609,7 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb)
 bool in_range(long long n) { return n >= 0 && n <= kNearestMax; }
 
 #include "nearest_k.h"
+#include "nearest_within.h"
 
 }  // namespace
 }  // namespace hidegs
@@ -724,4 +730,18 @@ extern "C" int hidegs_nearest_query_k(const void* index, size_t index_bytes, lon
                                       float* dist2_out, void* stream)
 {
     return hidegs::query_k(index, index_bytes, P, scratch, scratch_bytes, queries, Q, k, exclude, idx_out, dist2_out, stream);
+}
+
+extern "C" size_t hidegs_nearest_query_within_scratch_bytes(long long P, long long Q, int k)
+{
+    return hidegs::query_within_scratch_bytes(P, Q, k);
+}
+
+extern "C" int hidegs_nearest_query_within(const void* index, size_t index_bytes, long long P, void* scratch,
+                                           size_t scratch_bytes, const float* queries, long long Q, const float* r2, int k,
+                                           int max_count, const int32_t* exclude, int32_t* count_out, int32_t* idx_out,
+                                           float* dist2_out, void* stream)
+{
+    return hidegs::query_within(index, index_bytes, P, scratch, scratch_bytes, queries, Q, r2, k, max_count, exclude, count_out,
+                                idx_out, dist2_out, stream);
 }

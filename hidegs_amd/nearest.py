@@ -1,12 +1,17 @@
-"""Nearest-point index (include/hidegs_nearest.h, include/hidegs_nearest_k.h, csrc/nearest.hip): built once over a
-point cloud on the GPU, then asked for the nearest point, or the k nearest, of arbitrary positions -- exactly,
-lowest row index among equals.
+"""Nearest-point index (include/hidegs_nearest.h, include/hidegs_nearest_k.h, include/hidegs_nearest_within.h,
+csrc/nearest.hip): built once over a point cloud on the GPU, then asked for the nearest point, the k nearest, or
+how many points lie within a radius (and the k nearest of those) of arbitrary positions -- exactly, lowest row
+index among equals.
 
     index = NearestIndex(points)        # (P, 3) contiguous float32 GPU tensor; builds on the current stream
     idx, d2 = index.query(queries)      # (Q,) int32 (-1: none), (Q,) float32 squared distances
     idx, d2 = index.query_k(queries, k, exclude=None)   # (Q, k) each, nearest first; exclude: a row per query
     idx, d2 = nearest(points, queries)  # build + query
     idx, d2 = nearest_k(points, queries, k, exclude=None)
+    count, idx, d2 = index.query_within(queries, r2, k=0, exclude=None, max_count=None)   # (Q,), (Q, k), (Q, k)
+    count = index.count_within(queries, r2, exclude=None, max_count=None)   # r2: a number or a (Q,) tensor, squared
+    count, idx, d2 = within(points, queries, r2, k=0, exclude=None, max_count=None)
+    count = count_within(points, queries, r2, exclude=None, max_count=None)
 
 The index holds its own copy of the points: rebuild it after the positions move or the rows are resized.
 """
@@ -20,7 +25,7 @@ import torch
 from . import _lib
 
 _MAX = (1 << 31) - 1
-K_MAX = 64  # of query_k
+K_MAX = 64  # of query_k and query_within
 
 
 def _need_rows(t, what: str) -> int:
@@ -176,6 +181,98 @@ class NearestIndex:
             _lib.check(rc, "nearest_query_k")
         return idx, d2
 
+    def query_within(self, queries: torch.Tensor, r2, k: int = 0, exclude: torch.Tensor = None, max_count: int = None,
+                     out: Tuple[torch.Tensor, torch.Tensor, torch.Tensor] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(count, idx, d2) of the rows within a squared radius of every query.  r2: a Python number, the same
+        for every query, or a contiguous (Q,) float32 tensor on the index's device; a row is in range iff its
+        squared distance is <= r2 (inclusive; nothing is in range of a negative or NaN r2, everything of +inf).
+        count (Q,) int32: min(rows in range, max_count); max_count=None is 2^31 - 1, the exact count, and a
+        smaller one (at least max(k, 1)) lets a query stop once it has counted that many.  idx (Q, k) int32 and
+        d2 (Q, k) float32, 0 <= k <= 64: the k nearest of the rows in range, ascending by (distance, row); the
+        slots past them, and every slot of a query with a NaN or infinite coordinate (count 0), hold -1 and
+        +inf.  exclude: as for query_k; the excluded row is neither counted nor listed.  out=(count, idx, d2)
+        reuses three such tensors.  Runs on the current stream; no host synchronisation."""
+        Q = _need_rows(queries, "queries")
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise RuntimeError(f"nearest: k must be an integer, got {type(k).__name__}")
+        k = int(k)
+        if not 0 <= k <= K_MAX:
+            raise RuntimeError(f"nearest: k must be in [0, {K_MAX}], got {k}")
+        if max_count is None:
+            max_count = _MAX
+        if isinstance(max_count, bool) or not isinstance(max_count, numbers.Integral):
+            raise RuntimeError(f"nearest: max_count must be an integer or None, got {type(max_count).__name__}")
+        max_count = int(max_count)
+        if not max(k, 1) <= max_count <= _MAX:
+            raise RuntimeError(f"nearest: max_count must be in [max(k, 1), 2^31 - 1], got {max_count} with k = {k}")
+        if isinstance(r2, torch.Tensor):
+            if r2.dtype != torch.float32 or r2.dim() != 1 or not r2.is_contiguous():
+                raise RuntimeError(f"nearest: r2: expected a number or a contiguous 1-D float32 tensor, got {r2.dtype} of "
+                                   f"shape {tuple(r2.shape)}")
+            if r2.numel() != Q:
+                raise RuntimeError(f"nearest: r2 has {r2.numel()} entries, queries has {Q} rows")
+        elif isinstance(r2, bool) or not isinstance(r2, numbers.Real):
+            raise RuntimeError(f"nearest: r2 must be a number or a tensor, got {type(r2).__name__}")
+        if exclude is not None:
+            if not isinstance(exclude, torch.Tensor):
+                raise RuntimeError("nearest: exclude is not a tensor")
+            if exclude.dtype != torch.int32 or exclude.dim() != 1 or not exclude.is_contiguous():
+                raise RuntimeError(f"nearest: exclude: expected a contiguous 1-D int32 tensor, got {exclude.dtype} of "
+                                   f"shape {tuple(exclude.shape)}")
+            if exclude.numel() != Q:
+                raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise RuntimeError("nearest: out must be a triple (count, idx, d2)")
+            for what, t, dtype, shape in (("out count", out[0], torch.int32, (Q,)), ("out idx", out[1], torch.int32, (Q, k)),
+                                          ("out d2", out[2], torch.float32, (Q, k))):
+                if not isinstance(t, torch.Tensor):
+                    raise RuntimeError(f"nearest: {what} is not a tensor")
+                if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise RuntimeError(f"nearest: {what}: expected a contiguous {shape} {dtype} tensor, got "
+                                       f"{t.dtype} of shape {tuple(t.shape)}")
+        tensors = {"queries": queries}
+        if isinstance(r2, torch.Tensor):
+            tensors["r2"] = r2
+        if exclude is not None:
+            tensors["exclude"] = exclude
+        if out is not None:
+            tensors.update({"out count": out[0], "out idx": out[1], "out d2": out[2]})
+        if Q:
+            _lib.device_of(*tensors.values())
+        _need_gpu(self.device, **tensors)
+        with torch.cuda.device(self.device):
+            count, idx, d2 = out if out is not None else (torch.empty(Q, dtype=torch.int32, device=self.device),
+                                                          torch.empty((Q, k), dtype=torch.int32, device=self.device),
+                                                          torch.empty((Q, k), dtype=torch.float32, device=self.device))
+            if Q == 0:
+                return count, idx, d2
+            if not isinstance(r2, torch.Tensor):
+                r2 = torch.full((Q,), float(r2), dtype=torch.float32, device=self.device)  # a fill kernel: no synchronisation
+            L = _lib.lib()
+            stream = _lib.stream_handle(self.device)
+            tmp = None
+            if self.P:
+                # query's scratch tensors serve: the layout is the same
+                key = (stream, _size_class(Q))
+                need = L.hidegs_nearest_query_within_scratch_bytes(self.P, key[1], k)
+                tmp = self._scratch.get(key)
+                if tmp is None or tmp.numel() < need:
+                    tmp = self._scratch[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            rc = L.hidegs_nearest_query_within(_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp),
+                                               0 if tmp is None else tmp.numel(), queries.data_ptr(), Q, r2.data_ptr(), k,
+                                               max_count, _lib.ptr(exclude), count.data_ptr(),
+                                               idx.data_ptr() if k else None, d2.data_ptr() if k else None, stream)
+            _lib.check(rc, "nearest_query_within")
+        return count, idx, d2
+
+    def count_within(self, queries: torch.Tensor, r2, exclude: torch.Tensor = None, max_count: int = None) -> torch.Tensor:
+        """query_within(queries, r2, 0, exclude, max_count)[0]: (Q,) int32, how many rows lie within r2 of every
+        query, at most max_count.  `count_within(xyz, r2, exclude=arange(P), max_count=m) >= m` is radius outlier
+        removal's keep mask."""
+        return self.query_within(queries, r2, 0, exclude, max_count)[0]
+
 
 def nearest(points: torch.Tensor, queries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """NearestIndex(points).query(queries): for one set of queries against a cloud that will change."""
@@ -186,3 +283,15 @@ def nearest_k(points: torch.Tensor, queries: torch.Tensor, k: int, exclude: torc
               ) -> Tuple[torch.Tensor, torch.Tensor]:
     """NearestIndex(points).query_k(queries, k, exclude)."""
     return NearestIndex(points).query_k(queries, k, exclude)
+
+
+def within(points: torch.Tensor, queries: torch.Tensor, r2, k: int = 0, exclude: torch.Tensor = None, max_count: int = None
+           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """NearestIndex(points).query_within(queries, r2, k, exclude, max_count)."""
+    return NearestIndex(points).query_within(queries, r2, k, exclude, max_count)
+
+
+def count_within(points: torch.Tensor, queries: torch.Tensor, r2, exclude: torch.Tensor = None, max_count: int = None
+                 ) -> torch.Tensor:
+    """NearestIndex(points).count_within(queries, r2, exclude, max_count)."""
+    return NearestIndex(points).count_within(queries, r2, exclude, max_count)

@@ -5,6 +5,8 @@ check():  every output of the kernel against brute(), with bounds derived from t
 exact():  the bit-exact answer, in numpy, for inputs whose fp32 arithmetic is exact (small integers and
           half-integers): there every evaluation order and contraction gives the same bits.
 exact_on(): the same by torch on a device, for query sets too large for numpy's brute force.
+rounded_on(): the bit-exact answer for inputs that do round, by torch on a device: each fp32 rounding of the
+          contract's expression reproduced in float64 (fma32).
 """
 import numpy as np
 import torch
@@ -105,6 +107,56 @@ def exact_on(points, queries, device):
         idx[a:a + chunk] = torch.where(ok, best & 0xFFFFFFFF, -1).to(torch.int32)
         d2[a:a + chunk] = torch.where(ok, (best >> 32).to(torch.int32).view(torch.float32), float("inf"))
     return idx.cpu().numpy(), d2.cpu().numpy()
+
+
+def fma32(a, b, c):
+    """fmaf(a, b, c) of fp32 values held in float64 tensors (or numpy arrays), as float32: one rounding.
+    a * b is exact in float64 (two 24-bit factors).  Its sum with c is not always: where float64 rounds it, a
+    second rounding to fp32 could land on the other side of an fp32 midpoint.  So the float64 sum is rounded to
+    odd -- where TwoSum's error term is not zero and the sum's last bit is even, it is moved one float64 step
+    towards the error -- which keeps it off every fp32 midpoint and tie (29 bits further down) that the exact sum
+    is not on, and on the right side of them.  Finite normal values only."""
+    np_in = isinstance(a, np.ndarray)
+    a, b, c = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)) if np_in else x for x in (a, b, c))
+    assert a.dtype == b.dtype == c.dtype == torch.float64
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)  # TwoSum: p + c == s + err exactly
+    odd = (s.view(torch.int64) & 1) != 0
+    towards = torch.where(err > 0, float("inf"), -float("inf")).to(s.dtype)
+    s = torch.where((err != 0) & ~odd, torch.nextafter(s, towards), s)
+    out = s.float()
+    return out.numpy() if np_in else out
+
+
+def rounded_on(points, queries, device, k=1):
+    """(idx (Q, k) int32, d2 (Q, k) float32, ties (Q,) int64) as numpy arrays by the contract's rule -- the k
+    candidates with the smallest (bits(d), row), ascending, d = fmaf(dz, dz, fmaf(dx, dx, dy * dy)) on fp32
+    differences -- for inputs that round: every step's one rounding is reproduced in float64 (fma32), so the answer
+    is the kernel's in every bit, ties included.  ties: how many rows lie at the smallest distance.  For k <= P
+    finite points and finite queries whose squares neither overflow nor fall below the normal range."""
+    p = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)).to(device)
+    q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 3)).to(device)
+    P, Q = p.shape[0], q.shape[0]
+    assert P >= k >= 1 and bool(torch.isfinite(p).all()) and bool(torch.isfinite(q).all())
+    idx = torch.empty((Q, k), dtype=torch.int32, device=device)
+    d2 = torch.empty((Q, k), dtype=torch.float32, device=device)
+    ties = torch.empty(Q, dtype=torch.int64, device=device)
+    rows = torch.arange(P, dtype=torch.int64, device=device)
+    chunk = max(1, 30_000_000 // P)
+    for a in range(0, Q, chunk):
+        qq = q[a:a + chunk]
+        dx, dy, dz = ((p[None, :, c] - qq[:, None, c]).double() for c in range(3))  # fp32 differences: one rounding
+        t = (dy * dy).float().double()  # an exact product, rounded once
+        t = fma32(dx, dx, t).double()
+        d = fma32(dz, dz, t)
+        hi = d.view(torch.int32).to(torch.int64)  # d >= 0: the bits ascend
+        best = torch.topk((hi << 32) | rows[None, :], k, dim=1, largest=False, sorted=True).values
+        idx[a:a + chunk] = (best & 0xFFFFFFFF).to(torch.int32)
+        d2[a:a + chunk] = (best >> 32).to(torch.int32).view(torch.float32)
+        ties[a:a + chunk] = (hi == (best[:, :1] >> 32)).sum(1)
+    return idx.cpu().numpy(), d2.cpu().numpy(), ties.cpu().numpy()
 
 
 def exact(points, queries):

@@ -14,7 +14,8 @@ from hidegs_amd import _lib
 from hidegs_amd.resize import CLONED, resize_rows
 from test_resize_gpu import (EXTRA_SHAPES, FILL, LEAF_SHAPES, ROW_BATCH, SHAPES, UNITS_PER_WORKGROUP,
                              assert_same_optimizers, bits, keep_mask, leaf_optimizer, masked_step, params_of, payload,
-                             same_bits)
+                             same_bits, wide_keep, wide_sources)
+from test_rows_gpu import WIDE_N, WIDE_SCALAR, WIDE_VECTOR
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +91,29 @@ def test_other_widths_and_a_trailing_shape_at_a_ragged_size(built_lib):
         for f, t, out in zip(fields, tensors, outs):
             assert out.shape == (k + r * m, *SHAPES[f]) and out.is_contiguous()
             assert same_bits(out, expected(t, keep, clone, r)), f"field {SHAPES[f]}, clone {clone.dtype}"
+
+
+@pytest.mark.parametrize("k", [1, 9, "None"])
+def test_clones_of_rows_wider_than_a_workgroup_step(built_lib, k):
+    """test_resize_gpu's wide fields (widths 255 to 2052: step_j == 0 and step_c == 0 on the scalar and on the
+    16-byte path), every one cloned by a mask and by an index list with duplicates, twice over: the gather by keep
+    turns into the gather by from inside a row, and the second repeat starts inside a workgroup."""
+    widths = WIDE_VECTOR + WIDE_SCALAR
+    tensors, bufs = wide_sources()
+    before = [b.clone() for b in bufs]
+    keep = None if k == "None" else wide_keep(k, 70 + k)
+    kept = WIDE_N if keep is None else k
+    mask = wide_keep(5, 80)
+    index = torch.tensor([36, 0, 7, 7, 20, 36, 1], dtype=torch.int32, device="cuda")
+    for clone, m in ((mask, 5), (index, 7)):
+        with _lib.kernel_timer() as kt:
+            outs = resize_rows(tensors, keep, [CLONED] * len(widths), clone=clone, repeats=2)
+            torch.cuda.synchronize()
+        assert launches(kt) == (2, 0)
+        for w, t, out in zip(widths, tensors, outs):
+            assert out.shape == (kept + 2 * m, w)
+            assert same_bits(out, expected(t, keep, clone, 2)), f"k {k}, clone {clone.dtype}, width {w}"
+    assert all(torch.equal(bits(b), bits(was)) for b, was in zip(bufs, before)), "a source changed"
 
 
 def test_cloned_given_and_zero_fields_interleaved_over_two_launches(built_lib):

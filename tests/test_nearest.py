@@ -221,6 +221,49 @@ def test_the_torch_form_of_the_exact_oracle_equals_the_numpy_form():
     assert nearest_oracle.exact_on(pts[:0], qs, "cpu")[0].tolist() == [-1] * 900
 
 
+def test_the_float64_form_of_fmaf_equals_libm_in_every_bit():
+    """nearest_oracle.fma32 against the C library's fmaf: random operands whose sum float64 has to round (the addend
+    2^30 to 2^60 times the product or the reverse), and sums one float64 step off an fp32 midpoint, where rounding
+    twice gives the other neighbour."""
+    import ctypes.util
+    libm = ctypes.CDLL(ctypes.util.find_library("m"))
+    libm.fmaf.restype = ctypes.c_float
+    libm.fmaf.argtypes = [ctypes.c_float] * 3
+    g = np.random.default_rng(9)
+    n = 20_000
+    a = (g.standard_normal(n) * 2.0 ** g.integers(-20, 20, n)).astype(np.float32)
+    b = (g.standard_normal(n) * 2.0 ** g.integers(-20, 20, n)).astype(np.float32)
+    c = (g.standard_normal(n) * 2.0 ** g.integers(-20, 20, n)).astype(np.float32)
+    # c = 1 + 2^-23 m, whose upper midpoint is c + 2^-24, and a * b = (1 + 2^-23) 2^-24 (1 - 2^-23) = 2^-24 (1 - 2^-46):
+    # the exact sum lies 2^-70 below the midpoint, float64 rounds it onto the midpoint, and fp32's ties-to-even then
+    # goes up where m is odd.  Half of the cases mirrored to negative sums.
+    m = g.integers(0, 2 ** 23, 4_000)
+    sign = np.where(g.random(4_000) < 0.5, 1.0, -1.0)
+    cm = (sign * (1.0 + m * 2.0 ** -23)).astype(np.float32)
+    am = np.full(4_000, 1.0 + 2.0 ** -23, dtype=np.float32)
+    bm = (sign * 2.0 ** -24 * (1.0 - 2.0 ** -23)).astype(np.float32)
+    a, b, c = np.concatenate([a, am]), np.concatenate([b, bm]), np.concatenate([c, cm])
+    exp = np.array([libm.fmaf(x, y, z) for x, y, z in zip(a.tolist(), b.tolist(), c.tolist())], dtype=np.float32)
+    got = nearest_oracle.fma32(a.astype(np.float64), b.astype(np.float64), c.astype(np.float64))
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), exp.view(np.uint32))
+    twice = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+    assert (twice.view(np.uint32) != exp.view(np.uint32)).sum() > 500, "the cases were to include double roundings"
+
+
+def test_the_rounded_oracle_equals_the_exact_one_where_nothing_rounds():
+    g = np.random.default_rng(5)
+    pts = g.integers(0, 6, (700, 3)).astype(np.float32)  # many duplicates and ties
+    qs = (g.integers(-4, 16, (900, 3)) * 0.5).astype(np.float32)
+    a, b = nearest_oracle.exact(pts, qs), nearest_oracle.rounded_on(pts, qs, "cpu", 3)
+    assert np.array_equal(a[0], b[0][:, 0]) and np.array_equal(a[1].view(np.uint32), b[1][:, 0].view(np.uint32))
+    d = ((pts[None].astype(np.float64) - qs[:, None]) ** 2).sum(2)  # exact: small integers and halves
+    key = (d.astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.arange(700, dtype=np.uint64)
+    first = np.sort(key, 1)[:, :3]
+    assert np.array_equal(b[0], (first & np.uint64(0xFFFFFFFF)).astype(np.int32))
+    assert np.array_equal(b[1].view(np.uint32), (first >> np.uint64(32)).astype(np.uint32))
+    assert np.array_equal(b[2], (d == d.min(1, keepdims=True)).sum(1))
+
+
 def test_oracles_on_rows_and_queries_that_are_not_finite():
     pts = LATTICE.copy()
     pts[0, 1] = np.nan

@@ -23,6 +23,9 @@ from hidegs_amd.nearest import NearestIndex, nearest
 pytestmark = pytest.mark.gpu
 
 K_LEAF, K_FAN, K_WAVE, K_BAILOUT, K_SPAN_BAIL = 64, 64, 64, 256, 16
+K_HARD_GRID = 4096            # workgroups of a wave-per-query launch at most
+HARD_WAVES = K_HARD_GRID * 4  # its waves: above this many hard queries a wave takes a second one
+Q_TRIPS = (HARD_WAVES + 1, 2 * HARD_WAVES + 65)  # one wave's second trip; two for most, three for 65, a ragged workgroup
 WALK_BATCH = K_WAVE  # super-boxes per iteration of the s0 loop, in phase 1 and in phase 2
 SUPER_POINTS = K_LEAF * K_FAN
 
@@ -43,6 +46,11 @@ def test_restated_constants_match_nearest_hip():
                                 ("kWave", common))}
     assert found == {"kLeaf": K_LEAF, "kFan": K_FAN, "kBailout": K_BAILOUT, "kSpanBail": K_SPAN_BAIL, "kWave": K_WAVE}
     assert src.count("s0 += kWave)") == 2  # phase 1's walk and phase 2's
+    found = {name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1)) for name in ("kHardGrid", "kBlock")}
+    assert found["kHardGrid"] == K_HARD_GRID and HARD_WAVES == K_HARD_GRID * (found["kBlock"] // K_WAVE)
+    assert "constexpr int kWaves = kBlock / kWave;" in src
+    assert len(re.findall(r"nearest_hard_kernel, dim3\(std::min<unsigned>\(kHardGrid, \(unsigned\)ceil_div\(Q, kWaves\)\)\)", src)) == 1
+    assert src.count("h < nhard; h += nw)") == 1 and "nw = gridDim.x * kWaves;" in src
 
 
 def dev(a):
@@ -273,6 +281,63 @@ def test_far_outside_queries_take_the_hard_list(built_lib):
     print(f"plate, 256 queries 10^6 above it: {hard} took phase 2")
     assert hard == 256, "waves that pass the span test and list more than K_BAILOUT leaves"
     assert (idx == 0).all() and (d2 == 1e12).all()
+
+
+# ---- later trips of the wave-per-query loop ------------------------------------------------------------------
+PLATE_POINTS = 240_000
+
+
+@functools.lru_cache(maxsize=None)
+def plate_cloud():
+    """A thin wide plate, 1000 x 1000 x 0.01, its rows in random order."""
+    pts = np.random.default_rng(240).uniform(0, 1, (PLATE_POINTS, 3)).astype(np.float32) * np.array([1000, 1000, 0.01], dtype=np.float32)
+    pts.setflags(write=False)
+    return pts
+
+
+@functools.lru_cache(maxsize=None)
+def plate_queries(Q):
+    """Q queries 10^6 above the plate's inner part.  At 10^12 one ulp is 65,536, so a query's best distance ties over a
+    disc a few hundred units wide and every leaf that touches the disc has a bound at or below it: far more than
+    K_BAILOUT leaves (342 at least in a float64 model of 160,000 points), so every wave of phase 1 that passes the
+    span test overflows its list -- every query is a hard one.  The answer, the lowest row of the query's own disc,
+    differs from query to query."""
+    g = np.random.default_rng(Q)
+    qs = np.c_[g.uniform(100, 900, (Q, 2)), np.full(Q, 1e6)].astype(np.float32)
+    qs.setflags(write=False)
+    return qs
+
+
+@functools.lru_cache(maxsize=None)
+def plate_case(Q):
+    """(points, queries, exact idx (Q, 8), exact d2 (Q, 8), ties (Q,)): nearest_oracle.rounded_on reproduces every
+    fp32 rounding of the distance, so the expected rows and bits are the kernel's own where thousands of rows tie.
+    Formed once for the three queries' tests, at the k = 8 of the other two (about 2 s at 32,833 queries: 7.9 x 10^9
+    pairs)."""
+    pts, qs = plate_cloud(), plate_queries(Q)
+    idx, d2, ties = nearest_oracle.rounded_on(pts, qs, "cuda", 8)
+    for a in (idx, d2, ties):
+        a.setflags(write=False)
+    return pts, qs, idx, d2, ties
+
+
+@pytest.mark.parametrize("Q", Q_TRIPS)
+def test_more_hard_queries_than_waves(built_lib, Q):
+    """nearest_hard_kernel launches K_HARD_GRID workgroups at most: with more than HARD_WAVES hard queries its waves
+    take a second and a third one, and everything a wave keeps for a query (mine, best, the seed leaves) has to start
+    afresh.  Every query of the plate case is hard (16,385 of 16,385 and 32,833 of 32,833 on the MI355X), and each
+    is compared in index and bits with the rule of test_one_query_far_from_a_unit_cloud applied to all of them, and
+    with the float64 bounds."""
+    pts, qs, idx, d2, _ = plate_case(Q)
+    idx, d2 = idx[:, 0], d2[:, 0]
+    gi, gd, hard = raw_query(raw_build(dev(pts)), len(pts), dev(qs))
+    print(f"plate, {Q} queries: {hard} took phase 2; {len(np.unique(idx))} different rows are answers")
+    assert hard == Q and hard > (Q_TRIPS.index(Q) + 1) * HARD_WAVES
+    # 10^12 + t rounds to the lowest distance, 999,999,995,904, while t < 28,672: a row answers the queries within
+    # 169.3 units of it, 14.1% of the 800 x 800 square at most -- a result kept from a wave's previous query is wrong
+    assert (d2 == np.float32(999_999_995_904)).all() and np.bincount(idx).max() < Q // 6
+    assert_same((gi.cpu().numpy(), gd.cpu().numpy()), (idx, d2), f"plate, {Q} queries")
+    nearest_oracle.check(pts, qs, gi, gd, device="cuda")
 
 
 # ---- non-finite inputs --------------------------------------------------------------------------------------

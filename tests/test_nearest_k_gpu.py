@@ -21,7 +21,8 @@ import torch
 import nearest_k_oracle
 from hidegs_amd import _lib
 from hidegs_amd.nearest import NearestIndex, nearest_k
-from test_nearest_gpu import K_BAILOUT, K_LEAF, assert_same, bits, cloud, dev, lattice_case, mix, nsuper, raw_build, raw_query
+from test_nearest_gpu import (HARD_WAVES, K_BAILOUT, K_LEAF, Q_TRIPS, assert_same, bits, cloud, dev, lattice_case, mix, nsuper,
+                              plate_case, raw_build, raw_query)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +42,9 @@ def test_restated_constants_match_nearest_k_h():
     assert tuple(LANE_K_MAX if n == "kLaneKMax" else int(n) for n in launched) == LANE_KS
     assert re.findall(r"k <= (\w+)\)\n\s+launch_k_wave<(\w+)>", src) == [("4", "4"), ("8", "8"), ("kLaneKMax", "kLaneKMax")]
     assert src.count("s0 += kWave)") == 2  # the lane walk and the wave walk
+    # the wave-per-query launch is capped as the 1-NN query's (K_HARD_GRID and HARD_WAVES of test_nearest_gpu)
+    assert len(re.findall(r"nearest_k_hard_kernel, dim3\(std::min<unsigned>\(kHardGrid, \(unsigned\)ceil_div\(Q, kWaves\)\)\)", src)) == 1
+    assert src.count("h < nhard; h += nw)") == 1 and "nw = gridDim.x * kWaves;" in src
 
 
 def raw_query_k(index, P, queries_d, k, exclude_d=None, dirty=False):
@@ -296,6 +300,62 @@ def test_far_outside_queries_take_the_wave_path(built_lib):
     nearest_k_oracle.check_k(plate, above, k, None, idx, d2, device="cuda")
     assert hard == 256
     assert (idx.cpu().numpy() == np.arange(8)).all() and (d2 == 1e12).all()
+
+
+# ---- later trips of the wave-per-query loop ------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def trips_case(hard):
+    """The frustum cloud and hard + 10 mixed queries, ten of them not finite: they are not listed, so `hard` queries
+    are -- the count the trips depend on."""
+    Q = hard + 10
+    pts = cloud("frustum")
+    qs = mix(pts, Q, 50 + Q)
+    dead = np.random.default_rng(Q).choice(Q, 10, replace=False)
+    qs[dead, np.arange(10) % 3] = np.array([np.nan, np.inf, -np.inf], dtype=np.float32)[np.arange(10) % 3]
+    for a in (qs, dead):
+        a.setflags(write=False)
+    return pts, qs, dead
+
+
+@pytest.mark.parametrize("excluding", [False, True])
+@pytest.mark.parametrize("k", [LANE_K_MAX + 1, K_MAX])
+@pytest.mark.parametrize("finite", Q_TRIPS)
+def test_more_queries_above_the_lane_k_than_waves(built_lib, finite, k, excluding):
+    """Above LANE_K_MAX every finite query takes nearest_k_hard_kernel, which launches K_HARD_GRID workgroups at most:
+    with more than HARD_WAVES of them its waves take a second and a third query, and top, kth and the seed leaves
+    have to start afresh.  Every slot of every query against float64 brute force (2.3 x 10^9 pairs at 32,843
+    queries, about a second); with an exclusion it is the row the query would get first."""
+    pts, qs, dead = trips_case(finite)
+    Q = len(qs)
+    index = raw_build(dev(pts))
+    qd = dev(qs)
+    ex = None
+    if excluding:
+        first = raw_query_k(index, len(pts), qd, k)[0][:, 0]
+        ex = torch.where(torch.arange(Q, device="cuda") % 3 == 0, -1, first).to(torch.int32)  # -1: nothing excluded
+    idx, d2, hard = raw_query_k(index, len(pts), qd, k, ex)
+    assert hard == Q - 10 and hard > (Q_TRIPS.index(finite) + 1) * HARD_WAVES
+    other = nearest_k_oracle.check_k(pts, qs, k, None if ex is None else ex.cpu().numpy(), idx, d2, device="cuda")
+    print(f"{Q} queries, k {k}{', one row excluded' if excluding else ''}: {other} rows differ from the float64 order")
+    idx, d2 = host((idx, d2))
+    assert (idx[dead] == -1).all() and np.isposinf(d2[dead]).all()
+    live = np.delete(np.arange(Q), dead)
+    assert (idx[live] >= 0).all(), "a slot kept its sentinel or stayed empty"
+
+
+@pytest.mark.parametrize("Q", Q_TRIPS)
+def test_more_hard_queries_than_waves_on_the_lane_path_k(built_lib, Q):
+    """test_nearest_gpu.test_more_hard_queries_than_waves's plate at k = 8: every wave of the lane path overflows its
+    list, whatever k is, so all Q queries take the wave path (16,385 of 16,385 and 32,833 of 32,833 on the MI355X).
+    Thousands of rows tie at the lowest distance, so the answer is the eight lowest rows of the query's own disc in
+    every bit (nearest_oracle.rounded_on); the float64 bounds hold too (about 3 s at 32,833 queries)."""
+    k = 8
+    pts, qs, idx, d2, ties = plate_case(Q)
+    assert ties.min() > k and (d2 == d2[0, 0]).all()
+    gi, gd, hard = raw_query_k(raw_build(dev(pts)), len(pts), dev(qs), k)
+    assert hard == Q and hard > (Q_TRIPS.index(Q) + 1) * HARD_WAVES
+    assert_same(host((gi, gd)), (idx, d2), f"plate, {Q} queries, k {k}")
+    nearest_k_oracle.check_k(pts, qs, k, None, gi, gd, device="cuda")
 
 
 # ---- exclusion ----------------------------------------------------------------------------------------------

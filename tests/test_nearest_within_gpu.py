@@ -17,10 +17,27 @@ import torch
 import nearest_within_oracle as nwo
 from hidegs_amd import _lib
 from hidegs_amd.nearest import NearestIndex, count_within, within
-from test_nearest_gpu import K_BAILOUT, K_LEAF, assert_same, bits, cloud, dev, lattice_case, mix, nsuper, raw_build, raw_query
+from test_nearest_gpu import (HARD_WAVES, K_BAILOUT, K_LEAF, Q_TRIPS, assert_same, bits, cloud, dev, lattice_case, mix, nsuper,
+                              plate_case, raw_build, raw_query)
 from test_nearest_k_gpu import INT32_MIN, K_MAX, LANE_K_MAX, host, mech_case
 
 pytestmark = pytest.mark.gpu
+
+
+def test_restated_constants_match_nearest_within_h():
+    import os
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = open(os.path.join(here, "..", "hidegs_amd", "csrc", "nearest_within.h")).read()
+    assert re.findall(r"launch_within_wave<(\w+)>\(s,", src) == ["0", "4", "8", "kLaneKMax"]
+    assert re.findall(r"k (?:==|<=) (\w+)\)\n\s+launch_within_wave<(\w+)>", src) == [("0", "0"), ("4", "4"), ("8", "8"),
+                                                                                      ("kLaneKMax", "kLaneKMax")]
+    assert src.count("> kBailout)") == 1 and src.count("> kSpanBail)") == 1 and src.count("s0 += kWave)") == 2
+    # the wave-per-query launch is capped as the 1-NN query's (K_HARD_GRID and HARD_WAVES of test_nearest_gpu), in
+    # both forms: without a list at k = 0, with one above
+    assert src.count("const dim3 hgrid(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves)));") == 1
+    assert re.findall(r"nearest_within_hard_kernel<(\w+)>, hgrid,", src) == ["false", "true"]
+    assert src.count("h < nhard; h += nw)") == 1 and "nw = gridDim.x * kWaves;" in src
 
 INT32_MAX = 2 ** 31 - 1
 INF, NAN = float("inf"), float("nan")
@@ -289,6 +306,109 @@ def test_an_infinite_radius_sends_every_wave_to_the_wave_path(built_lib):
     count, idx, d2, hard = raw_within(index, len(pts), dev(qs), r2, LANE_K_MAX + 1)
     assert hard == int((fin & (r2 >= 0)).sum()) and (count[r2 < 0] == 0).all() and (idx[r2 < 0] == -1).all()
     nwo.check_within(pts, qs, r2, LANE_K_MAX + 1, None, None, count, idx, d2, device="cuda")
+
+
+# ---- later trips of the wave-per-query loop ------------------------------------------------------------------
+TRIPS_POINTS = 40_000  # 625 leaves: a lane-path wave that has to list them all overflows K_BAILOUT (12,289 points are 193)
+N_DEAD = 9             # planted queries that are answered without being listed
+
+
+@functools.lru_cache(maxsize=None)
+def trips_cloud():
+    pts = np.random.default_rng(TRIPS_POINTS).uniform(1, 9, (TRIPS_POINTS, 3)).astype(np.float32)
+    pts.setflags(write=False)
+    return pts
+
+
+def plant(g, Q, qs, r2):
+    """N_DEAD queries that nothing is in range of -- NaN and negative radii, one position not finite -- and as many
+    with a radius of zero, which are listed like their neighbours.  Returns the dead ones."""
+    where = g.choice(Q, 2 * N_DEAD, replace=False)
+    dead, zero = where[:N_DEAD], where[N_DEAD:]
+    r2[dead] = np.array([NAN, -1.0, -INF, NAN, -0.5, -1e-30, NAN, -2.0, 1.0], dtype=np.float32)
+    qs[dead[-1], 1] = NAN
+    r2[zero] = np.array([0.0, -0.0] * N_DEAD, dtype=np.float32)[:N_DEAD]
+    return dead
+
+
+@functools.lru_cache(maxsize=None)
+def trips_case(setting, listed):
+    """(points, queries, r2, k, max_count, dead) with listed + N_DEAD queries, of which `listed` reach the wave path.
+
+    "inf", "inf, k 8": mixed queries in and around the cloud with an infinite radius.  On the lane path such a wave
+    has to list every leaf, 622 after its seed, and bails out.
+    "radii": the same queries with radii of 10 to 14 units against a cloud 8 units wide: the counts differ from query
+    to query, and the largest radius of a wave still reaches far more than K_BAILOUT leaves.
+    "capped": k = 0 with max_count = 8.  On the lane path an infinite radius is saturated by the seed's 192 points and
+    the wave stays there, so this set is built differently: every query lies beyond the cloud's far corner, (9, 9, 9),
+    where all keys clamp to the same cell.  A quarter of them, at 20 to 21 on every axis, have r2 = 300: below their
+    distance to any point (363 at least), so their count stays 0 and they stay open, and above the distance from a
+    wave's box to any leaf (243 at most from a box that reaches below 10), so the wave lists every leaf and bails out.
+    The others lie within a unit of the corner, with an infinite radius (saturated by the first leaf on the wave
+    path: the early exit) or one of 0 to 2 units (counts around 8, on both sides)."""
+    g = np.random.default_rng(listed + len(setting))
+    pts = trips_cloud()
+    Q = listed + N_DEAD
+    k, max_count = (8 if setting == "inf, k 8" else 0), (8 if setting == "capped" else None)
+    if setting == "capped":
+        qs = g.uniform(9.05, 10.0, (Q, 3)).astype(np.float32)
+        r2 = np.where(g.random(Q) < 0.5, INF, g.uniform(0.0, 4.0, Q)).astype(np.float32)
+        far = g.random(Q) < 0.25
+        qs[far] = g.uniform(20.0, 21.0, (int(far.sum()), 3)).astype(np.float32)
+        r2[far] = 300.0
+    else:
+        qs = mix(pts, Q, Q)
+        r2 = np.full(Q, INF, dtype=np.float32) if setting.startswith("inf") else (g.uniform(10.0, 14.0, Q) ** 2).astype(np.float32)
+    dead = plant(g, Q, qs, r2)
+    for a in (qs, r2, dead):
+        a.setflags(write=False)
+    return pts, qs, r2, k, max_count, dead
+
+
+@pytest.mark.parametrize("setting", ["inf", "capped", "radii", "inf, k 8"])
+@pytest.mark.parametrize("listed", Q_TRIPS)
+def test_more_hard_queries_than_waves(built_lib, listed, setting):
+    """nearest_within_hard_kernel<false> (k = 0) and <true> launch K_HARD_GRID workgroups at most: with more than
+    HARD_WAVES hard queries a wave takes a second and a third one, and count, top, kth, bnd and the seed leaves have
+    to start afresh -- after a query that ran to the end, one that left every loop saturated, and one whose count
+    stayed 0.  Every query against float64 brute force over all rows (1.3 x 10^9 pairs at 32,842 queries)."""
+    pts, qs, r2, k, max_count, dead = trips_case(setting, listed)
+    Q = len(qs)
+    got = raw_within(raw_build(dev(pts)), len(pts), dev(qs), r2, k, INT32_MAX if max_count is None else max_count)
+    count, idx, d2, hard = got
+    assert hard == listed == Q - N_DEAD and hard > (Q_TRIPS.index(listed) + 1) * HARD_WAVES
+    assert count.min() >= 0, "a count kept its sentinel"
+    band, capped = nwo.check_within(pts, qs, r2, k, max_count, None, count, idx, d2, device="cuda")
+    print(f"{setting}, {Q} queries: {hard} took the wave path; {band} with a row in the band, {capped} capped; "
+          f"{len(np.unique(count))} different counts")
+    assert (count >= 0).all() and (count[dead] == 0).all() and (idx[dead] == -1).all() and np.isposinf(d2[dead]).all()
+    live = np.delete(np.arange(Q), dead)
+    if setting.startswith("inf"):
+        assert (count[live][r2[live] == INF] == len(pts)).all() and (count[live][r2[live] == 0] <= 1).all()
+    if setting == "radii":
+        assert len(np.unique(count)) > 1_000
+    if setting == "capped":
+        far = qs[:, 0] >= 20
+        assert (count[far & (r2 == 300)] == 0).all() and (count[live][r2[live] == INF] == 8).all()
+        some = count[~far & np.isfinite(r2) & (r2 > 0)]
+        assert (some == 8).sum() > Q // 100 and (some < 8).sum() > Q // 100 and len(np.unique(some)) == 9
+
+
+@pytest.mark.parametrize("Q", Q_TRIPS)
+def test_more_hard_queries_than_waves_with_a_finite_radius(built_lib, Q):
+    """test_nearest_gpu.test_more_hard_queries_than_waves's plate at k = 8 with the lowest distance, 999,999,995,904,
+    as every query's radius: the radius reaches the leaves of the query's tie disc, far more than K_BAILOUT, so every
+    wave of the lane path bails out (16,385 of 16,385 and 32,833 of 32,833 queries on the MI355X).  In range are
+    exactly the rows that tie, thousands and another number for every query, and the list is the eight lowest of
+    them: count, rows and distances in every bit against nearest_oracle.rounded_on, and the float64 band."""
+    k = 8
+    pts, qs, idx, d2, ties = plate_case(Q)
+    r2 = float(d2[0, 0])
+    assert r2 == 999_999_995_904.0 and (d2 == d2[0, 0]).all() and ties.min() > k and len(np.unique(ties)) > Q // 10
+    count, gi, gd, hard = raw_within(raw_build(dev(pts)), len(pts), dev(qs), r2, k)
+    assert hard == Q and hard > (Q_TRIPS.index(Q) + 1) * HARD_WAVES
+    assert_same3((count, gi, gd), (ties.astype(np.int32), idx, d2), f"plate, {Q} queries, k {k}")
+    nwo.check_within(pts, qs, r2, k, None, None, count, gi, gd, device="cuda")
 
 
 # ---- edges --------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import torch
 from hidegs_amd import _lib, optim
 from hidegs_amd.resize import resize_rows
 from hidegs_amd.view_dp import LEAF_WIDTHS, GradArena
+from test_rows_gpu import WIDE_N, WIDE_SCALAR, WIDE_VECTOR, wide_image, wide_tensors
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +185,85 @@ def test_an_index_past_the_rows_gives_a_zero_row(built_lib):
             else:
                 assert not bits(dst[j]).any(), f"dst row {j} (index {i} >= {n_rows}) is not all zero bits"
         assert not bits(dst[k:]).any()
+
+
+# ---- rows wider than a workgroup step -------------------------------------------------------------------
+def wide_sources():
+    """test_rows_gpu's wide fields: nine (37, w) sources, w from 255 to 2052, the 16-byte path's on 16 bytes and
+    the scalar path's multiples of 4 one float past them, so that step_j == 0 and step_c == 0 run on both paths."""
+    tensors, bufs = wide_tensors(wide_image())
+    for t, w in zip(tensors, WIDE_VECTOR + WIDE_SCALAR):
+        unit = 4 if w in WIDE_VECTOR else 1
+        assert (w % 4 == 0 and t.data_ptr() % 16 == 0) == (unit == 4)  # resize_field's rule: dst is torch's, on 16 bytes
+    return tensors, bufs
+
+
+def wide_keep(k, seed):
+    mask = torch.zeros(WIDE_N, dtype=torch.bool)
+    mask[torch.randperm(WIDE_N, generator=torch.Generator().manual_seed(seed))[:k]] = True
+    return mask.cuda()
+
+
+@pytest.mark.parametrize("k", [1, 9, 17, "None"])
+def test_resize_of_rows_wider_than_a_workgroup_step(built_lib, k):
+    """A keep mask of k rows or no keep at all; appended rows given (the first five fields) and zero-filled (the
+    others) in one call, append only, and prune only.  With k = 9 and 17 the seam between gathered and appended units
+    lies inside a workgroup, and inside a row's span of it, on every field."""
+    widths = WIDE_VECTOR + WIDE_SCALAR
+    tensors, bufs = wide_sources()
+    before = [b.clone() for b in bufs]
+    keep = None if k == "None" else wide_keep(k, 60 + k)
+    kept = WIDE_N if keep is None else k
+    if kept in (9, 17):
+        for w in widths:
+            seam = kept * w // (4 if w in WIDE_VECTOR else 1)
+            assert seam % UNITS_PER_WORKGROUP, w  # not on a workgroup's edge
+    for a in (0, 5):
+        g = torch.Generator().manual_seed(a)
+        new = [torch.randint(-2**31, 2**31, (a, w), generator=g, dtype=torch.int64).to(torch.int32).view(torch.float32).cuda()
+               if f < 5 else None for f, w in enumerate(widths)]
+        assert all(t is None or t.data_ptr() % 16 == 0 for t in new)
+        with _lib.kernel_timer() as kt:
+            outs = resize_rows(tensors, keep, new if a else None, None if a else 0)
+            torch.cuda.synchronize()
+        assert kt.get("resize_rows")[1] == 2
+        for w, t, n_, out in zip(widths, tensors, new, outs):
+            assert out.shape == (kept + a, w)
+            assert same_bits(out, expected(t, keep, n_ if a else None, a)), f"k {k}, append {a}, width {w}"
+    if keep is not None:  # append only: no row kept
+        none = torch.zeros(WIDE_N, dtype=torch.bool, device="cuda")
+        outs = resize_rows(tensors, none, new)
+        for w, n_, out in zip(widths, new, outs):
+            assert same_bits(out, n_) if n_ is not None else (out.shape == (5, w) and not bits(out).any()), f"append only, width {w}"
+    assert all(torch.equal(bits(b), bits(was)) for b, was in zip(bufs, before)), "a source changed"
+
+
+def test_a_keep_index_into_wide_rows_and_one_past_them(built_lib):
+    """test_an_index_past_the_rows_gives_a_zero_row's call on the wide fields: a keep list in no order, with
+    duplicates, and with two entries at or past n_rows, whose rows are zeros; two zero rows appended."""
+    widths = WIDE_VECTOR + WIDE_SCALAR
+    srcs, _ = wide_sources()
+    a = 2
+    index = [0, 5, WIDE_N, 7, 4_000_000_000, WIDE_N - 1, 3, WIDE_N - 1, 1]
+    k = len(index)
+    keep = torch.tensor([i - (1 << 32) if i >= 1 << 31 else i for i in index], dtype=torch.int32, device="cuda")
+    fields = (_lib.ResizeField * len(widths))()
+    dsts = [torch.empty(k + a, w, device="cuda") for w in widths]
+    for f, src, dst in zip(fields, srcs, dsts):
+        bits(dst).fill_(FILL)
+        f.src, f.append, f.dst, f.n_rows, f.width = src.data_ptr(), None, dst.data_ptr(), WIDE_N, dst.shape[1]
+    with _lib.kernel_timer() as kt:
+        rc = built_lib.hidegs_resize_rows(ctypes.cast(fields, ctypes.c_void_p), len(widths), keep.data_ptr(), k, a,
+                                          _lib.stream_handle(keep.device))
+        _lib.check(rc, "resize_rows")
+        torch.cuda.synchronize()
+    assert kt.get("resize_rows")[1] == 2
+    for w, src, dst in zip(widths, srcs, dsts):
+        rows = torch.tensor([i if i < WIDE_N else 0 for i in index], device="cuda")
+        want = bits(src)[rows].clone()
+        want[[j for j, i in enumerate(index) if i >= WIDE_N]] = 0
+        assert torch.equal(bits(dst[:k]), want), f"width {w}"
+        assert not bits(dst[k:]).any(), f"width {w}: the appended rows are not zeros"
 
 
 def test_runs_on_current_stream_after_the_work_queued_there(built_lib):

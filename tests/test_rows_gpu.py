@@ -250,6 +250,122 @@ def test_row_moves_take_the_vector_path_only_where_every_row_is_aligned():
     assert units(NINE_WIDTHS, N_ALIGNED, 1000) == [1, 1, 1, 4, 1, 4, 1, 4, 1]
 
 
+# ---- rows wider than a workgroup step -------------------------------------------------------------------
+# A thread's consecutive units lie kBlock * unit floats apart: step_j = (256 * unit) // width rows and
+# step_c = (256 * unit) % width columns.  Every width above is at most 64.  These put the scalar path on both sides of
+# 256 floats (step_c == 0 at 256, step_j == 0 above it) and the 16-byte path on both sides of 1024.
+WIDE_SCALAR = [255, 256, 257, 300, 1025]  # 256 and 300 are multiples of 4: their row side starts one float off 16 bytes
+WIDE_VECTOR = [1020, 1024, 1028, 2052]
+WIDE_N = 37
+WIDE_KS = [1, 2, 9, 17, 37]
+UNITS_PER_WORKGROUP = 2048  # rows.hip kUnitsPerBlock: 256 threads x 8 units
+
+
+def wide_steps(width, unit):
+    """(step_j, step_c) of rows.hip's RowField / ResizeField."""
+    return (256 * unit) // width, (256 * unit) % width
+
+
+def wide_tensors(image, fill=None):
+    """[(n, w) device views] of `image`'s rows, field by field in the order WIDE_VECTOR + WIDE_SCALAR, each in a buffer
+    of its own with 8 floats of FILL behind it: the 16-byte path's fields on 16 bytes, the scalar path's multiples of 4
+    one float past them; and the buffers.  With `fill`, the rows hold it instead of the image."""
+    views, bufs, off = [], [], 0
+    for w in WIDE_VECTOR + WIDE_SCALAR:
+        shift = 1 if w in WIDE_SCALAR and w % 4 == 0 else 0
+        buf = torch.full((WIDE_N * w + 8,), FILL, dtype=torch.int32)
+        buf[shift:shift + WIDE_N * w] = image[off:off + WIDE_N * w] if fill is None else fill
+        buf = buf.cuda().view(torch.float32)
+        view = buf[shift:shift + WIDE_N * w].view(WIDE_N, w)
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * shift and view.is_contiguous()
+        views.append(view)
+        bufs.append(buf)
+        off += WIDE_N * w
+    return views, bufs
+
+
+@functools.lru_cache(maxsize=None)
+def wide_image():
+    """host_arena's kind of image for the wide fields: random bit patterns with SPECIAL_BITS planted in every field."""
+    widths = WIDE_VECTOR + WIDE_SCALAR
+    g = torch.Generator().manual_seed(sum(widths))
+    flat = torch.randint(-2**31, 2**31, (WIDE_N * sum(widths),), generator=g, dtype=torch.int64).to(torch.int32)
+    for f, view in enumerate(field_views(flat, dict(enumerate(widths)), WIDE_N)):
+        for i, b in enumerate(SPECIAL_BITS):
+            for r in (0, 1, WIDE_N // 2 + i, WIDE_N - 1):
+                view[r, (i + f + r) * 97 % view.shape[1]] = signed(b)
+    return flat
+
+
+def test_wide_rows_reach_both_paths_on_both_sides_of_a_workgroup_step():
+    """What the wide shapes exercise, from the rule in rows.hip's move_rows (unit = 4 iff width % 4 == 0 and both bases
+    are on 16 bytes; the packed field of width w starts k * (the widths before it) floats into an aligned buffer)."""
+    def units(k):
+        out, packed_off = [], 0
+        for w in WIDE_VECTOR + WIDE_SCALAR:
+            rows_shift = 1 if w in WIDE_SCALAR and w % 4 == 0 else 0
+            out.append(4 if w % 4 == 0 and rows_shift == 0 and (4 * packed_off) % 16 == 0 else 1)
+            packed_off += k * w
+        return out
+    for k in WIDE_KS:
+        assert units(k) == [4] * len(WIDE_VECTOR) + [1] * len(WIDE_SCALAR), k
+    assert len(WIDE_VECTOR + WIDE_SCALAR) > ROW_BATCH  # two launches
+    scalar = {w: wide_steps(w, 1) for w in WIDE_SCALAR}
+    vector = {w: wide_steps(w, 4) for w in WIDE_VECTOR}
+    assert scalar == {255: (1, 1), 256: (1, 0), 257: (0, 256), 300: (0, 256), 1025: (0, 256)}
+    assert vector == {1020: (1, 4), 1024: (1, 0), 1028: (0, 1024), 2052: (0, 1024)}
+    # k * width crosses no workgroup edge, one, two, and more on either path
+    for widths, unit in ((WIDE_SCALAR, 1), (WIDE_VECTOR, 4)):
+        crossed = {(k * w // unit - 1) // UNITS_PER_WORKGROUP for w in widths for k in WIDE_KS}
+        assert {0, 1, 2, 4} <= crossed, (unit, crossed)
+
+
+@pytest.mark.parametrize("k", WIDE_KS)
+def test_gather_and_scatter_of_rows_wider_than_a_workgroup_step(built_lib, k):
+    widths = dict(enumerate(WIDE_VECTOR + WIDE_SCALAR))
+    row_width = sum(widths.values())
+    image = wide_image()
+    src_fields = field_views(image, widths, WIDE_N)
+    tensors, bufs = wide_tensors(image)
+    before = [b.view(torch.int32).cpu() for b in bufs]
+    g = torch.Generator().manual_seed(k)
+    for name, rows in row_sets(WIDE_N, k).items():
+        what = f"k {k}, {name} rows"
+        rows_dev = rows.to(torch.int32).cuda()
+        out = torch.full((k * row_width + 3,), 0.0, device="cuda")
+        out.view(torch.int32).fill_(FILL)
+        assert out.data_ptr() % 16 == 0
+        with _lib.kernel_timer() as kt:
+            assert wire.gather_rows(tensors, rows_dev, out) is out
+            torch.cuda.synchronize()
+        assert kt.get("gather_rows")[1] == 2, what
+        exp = torch.cat([torch.index_select(f, 0, rows).reshape(-1) for f in src_fields])
+        got = out.view(torch.int32).cpu()
+        assert torch.equal(got[:k * row_width], exp), f"{what}: gather differs from index_select"
+        assert bool((got[k * row_width:] == FILL).all()), f"{what}: gather wrote past the packed rows"
+        assert all(torch.equal(b.view(torch.int32).cpu(), was) for b, was in zip(bufs, before)), f"{what}: gather changed a source"
+        # scatter == index_copy_ per field into destinations that hold FILL everywhere else
+        packed = torch.randint(-2**31, 2**31, (k * row_width,), generator=g, dtype=torch.int64).to(torch.int32)
+        special = torch.tensor([signed(b) for b in SPECIAL_BITS], dtype=torch.int32)
+        packed[::5] = special[torch.arange(packed[::5].numel()) % len(SPECIAL_BITS)]
+        dest, dest_bufs = wide_tensors(image, fill=FILL)
+        with _lib.kernel_timer() as kt:
+            wire.scatter_rows(dest, rows_dev, packed.cuda().view(torch.float32))
+            torch.cuda.synchronize()
+        assert kt.get("scatter_rows")[1] == 2, what
+        for w, d, buf, p in zip(widths.values(), dest, dest_bufs, field_views(packed, widths, k)):
+            exp_dest = torch.full((WIDE_N, w), FILL, dtype=torch.int32)
+            exp_dest.index_copy_(0, rows, p)
+            assert torch.equal(d.view(torch.int32).cpu(), exp_dest), \
+                f"{what}, width {w}: scatter differs from index_copy_ (or touched a row that was not named)"
+            shift, flat = d.data_ptr() % 16 // 4, buf.view(torch.int32)
+            assert bool((flat[:shift] == FILL).all()) and bool((flat[shift + WIDE_N * w:] == FILL).all()), \
+                f"{what}, width {w}: a float outside the rows changed"
+        # scatter after gather leaves the sources as they were
+        wire.scatter_rows(tensors, rows_dev, out)
+        assert all(torch.equal(b.view(torch.int32).cpu(), was) for b, was in zip(bufs, before)), f"{what}: scatter after gather"
+
+
 def test_row_move_wrappers_check_their_arguments(built_lib):
     t = torch.zeros(10, 3, device="cuda")
     rows = torch.arange(4, dtype=torch.int32, device="cuda")

@@ -120,6 +120,103 @@ def test_both_forms_of_the_tie_offsets(built_lib, n):
         check(scores, None, ks, f"n {n}, {name}", rank, scores_d=sd)
 
 
+# ---- later trips of the digit passes ---------------------------------------------------------------------
+HIST_GRID = 2048  # topk.hip kHistGrid: workgroups of a digit pass at most; above it they stride over the tiles
+# the last size with one trip; workgroup 0's second tile, of one row; 4,098 tiles: a third trip for workgroups 0 and 1,
+# a ragged last tile, and a scan of the tie counts in two steps of 4,096
+TRIPS = [HIST_GRID * TILE, HIST_GRID * TILE + 1, 2 * HIST_GRID * TILE + TILE + 5]
+TRIP_SETS = ["normal", "all equal, +0.0 and -0.0", "two alternating values", "equal but in the later tiles"]
+
+
+def test_restated_constants_match_topk_hip():
+    import os
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = open(os.path.join(here, "..", "hidegs_amd", "csrc", "topk.hip")).read()
+    scan = open(os.path.join(here, "..", "hidegs_amd", "csrc", "block_scan.h")).read()
+    found = {name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1)) for name in ("kHistGrid", "kOwnTiles", "kItems", "kBlock")}
+    assert found == {"kHistGrid": HIST_GRID, "kOwnTiles": OWN_TILES, "kItems": TILE // 256, "kBlock": 256}
+    assert "constexpr int kTile = kBlock * kItems;" in src
+    assert "const dim3 hist_grid(nt < kHistGrid ? nt : kHistGrid), block(kBlock);" in src
+    assert src.count("tile < ntiles; tile += gridDim.x)") == 1 and len(re.findall(r"topk_hist_kernel<\d>, hist_grid,", src)) == 4
+    block, items = (int(re.search(r"constexpr int %s = (\d+);" % name, scan).group(1)) for name in ("kScanBlock", "kScanItems"))
+    assert "constexpr int kScanTile = kScanBlock * kScanItems;" in scan and "base < count; base += kScanTile)" in scan
+    assert block * items == 4096 < -(-TRIPS[2] // TILE)  # scan_small_kernel's second step, for top-k's tie counts
+
+
+def trip_scores(n, name):
+    """The fourth set is 0.0 everywhere but in the tiles from HIST_GRID on, which hold a normal sample behind one 2.5:
+    for a k up to the positive scores' number the threshold and every selected row lie in tiles that only the later
+    trips read."""
+    if name != TRIP_SETS[3]:
+        return datasets(n, full=False)[name]
+    scores = np.zeros(n, dtype=np.float32)
+    scores[HIST_GRID * TILE:] = np.random.default_rng(n).standard_normal(n - HIST_GRID * TILE).astype(np.float32)
+    if n > HIST_GRID * TILE:
+        scores[HIST_GRID * TILE] = 2.5
+    return scores
+
+
+def trip_ks(n, name, rank):
+    """0, 1, n // 3, n - TILE - 1, n, K_MAX and four edges of tie groups from ks_for.  Past HIST_GRID * TILE rows some
+    tie quota has to end in a tile of a later trip: with equal scores the quota is k itself (n - TILE - 1, in the last
+    full tile), the higher of two alternating values lies on the even rows, so a quota above HIST_GRID * TILE / 2
+    ends past row HIST_GRID * TILE (n // 3 at the largest size, and one added), and the fourth set's positive scores
+    all lie there."""
+    ks = [0, 1, n // 3, n - TILE - 1, n, K_MAX]
+    edges = [k for k in ks_for(rank) if k not in ks and 1 < k < n]
+    ks += edges[::max(1, len(edges) // 4)][:4]
+    if n > HIST_GRID * TILE + 1:
+        assert n - TILE - 1 > HIST_GRID * TILE and n // 3 > HIST_GRID * TILE // 2
+        if name == TRIP_SETS[2]:
+            ks.append(HIST_GRID * TILE // 2 + 10)
+    if name == TRIP_SETS[3]:
+        positive = int((rank.keys > 0x80000000).sum())
+        assert positive >= (n > HIST_GRID * TILE)
+        ks += [max(positive // 2, 1), positive, positive + 1, positive + HIST_GRID * TILE // 2]
+    return sorted(set(ks))
+
+
+@pytest.mark.parametrize("name", TRIP_SETS)
+@pytest.mark.parametrize("n", TRIPS)
+def test_more_tiles_than_workgroups_of_a_digit_pass(built_lib, n, name):
+    """topk_hist_kernel launches HIST_GRID workgroups at most, which stride over the tiles: above HIST_GRID * TILE
+    rows a workgroup counts a second and a third tile into the same LDS bins.  A pass that dropped them would lose
+    candidates (info[1] < n) and, with the fourth set, the threshold itself.  The host oracle's stable argsort makes
+    the case of 16.8M normal scores take 3 s; the equal and the alternating sets are sorted in a fraction of that."""
+    scores = trip_scores(n, name)
+    rank = topk_oracle.Ranking(scores)
+    assert -(-n // TILE) == {TRIPS[0]: HIST_GRID, TRIPS[1]: HIST_GRID + 1, TRIPS[2]: 2 * HIST_GRID + 2}[n] and rank.c == n
+    sd = torch.from_numpy(scores).cuda()
+    with _lib.kernel_timer() as kt:
+        _, info = primitives.top_k_mask(sd, n // 3)
+        torch.cuda.synchronize()
+    assert kt.get("topk_hist")[1] == 4 and kt.get("topk_offsets")[1] == 1
+    assert kt.get("topk_tie_count")[1] == 1 and kt.get("topk_write")[1] == 1
+    assert info.cpu().tolist()[1] == n, "a digit pass did not count every row"
+    check(scores, None, trip_ks(n, name, rank), f"n {n}, {name}", rank, scores_d=sd)
+
+
+def test_later_trips_with_a_candidate_mask_and_with_unaligned_scores(built_lib):
+    """`among` once at the largest size (its bytes are read by the later trips too), and a scores view one element
+    off 16 bytes at HIST_GRID * TILE + 1, where every tile of both trips takes the scalar loads."""
+    n = TRIPS[2]
+    scores = trip_scores(n, "normal")
+    among = np.random.default_rng(n).random(n) < 0.4
+    among[HIST_GRID * TILE - 5:HIST_GRID * TILE + TILE] = True
+    rank = topk_oracle.Ranking(scores, among)
+    check(scores, among, [1, rank.c // 3, rank.c - 1, rank.c, K_MAX], f"n {n}, among", rank)
+    n = TRIPS[1]
+    scores = trip_scores(n, TRIP_SETS[3])
+    rank = topk_oracle.Ranking(scores)
+    sbuf = torch.zeros(n + 8, dtype=torch.float32, device="cuda")
+    assert sbuf.data_ptr() % 16 == 0
+    sd = sbuf[1:1 + n]
+    sd.copy_(torch.from_numpy(scores))
+    assert sd.data_ptr() % 16 == 4
+    check(scores, None, [1, 2, n // 3, n - 1, n], f"n {n}, scores one element off 16 bytes", rank, scores_d=sd)
+
+
 def test_equal_scores_select_the_first_candidates(built_lib):
     """All scores equal: the first k candidate rows, at a size where a serialised histogram would not finish."""
     n = 2**20

@@ -32,7 +32,10 @@
 //
 // Two further queries on the same index are stages of this file, included below inside its namespace: the k
 // nearest (nearest_k.h) and the count and the k nearest within a radius (nearest_within.h).  Neither adds to
-// the build or to the scratch layout.
+// the build or to the scratch layout.  What the three share is written once, here: phase 1 is lane_walk, a
+// template over what a lane keeps (its searcher: LaneBest here, LaneK and LaneWithin there), and every entry
+// point begins with begin_query (argument checks, the empty cloud, the query keys and their sort).  Phase 2 of
+// the two list queries is one walk of their own (nearest_k.h's hard_list_walk).
 #include <float.h>
 #include <stdint.h>
 
@@ -344,11 +347,10 @@ __device__ __forceinline__ void push_hard(bool flag, long long s, int lane, uint
     if (flag) hard[at + __popcll(m & lanes_below(lane))] = (uint32_t)s;
 }
 
-// best = min(best, candidate k) for the point held by lane k of `pt`, broadcast to every lane.
-__device__ __forceinline__ void eval_lane(float4 pt, int k, float4 q, uint64_t& best)
+// The point held by lane c of `pt`, broadcast to every lane.
+__device__ __forceinline__ float4 lane_point(float4 pt, int c)
 {
-    const float4 c = make_float4(uniform_lane(pt.x, k), uniform_lane(pt.y, k), uniform_lane(pt.z, k), uniform_lane(pt.w, k));
-    best = min(best, pack(sqdist(q, c), c.w));
+    return make_float4(uniform_lane(pt.x, c), uniform_lane(pt.y, c), uniform_lane(pt.z, c), uniform_lane(pt.w, c));
 }
 
 __device__ __forceinline__ void store_result(uint64_t best, long long j, int32_t* __restrict__ idx_out,
@@ -360,10 +362,22 @@ __device__ __forceinline__ void store_result(uint64_t best, long long j, int32_t
     dist2_out[j] = none ? INFINITY : __uint_as_float(d);
 }
 
-__global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
-                                                              const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
-                                                              int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
-                                                              uint32_t* __restrict__ hard, Counters* __restrict__ counters)
+// Phase 1 for every query of this file: one wave per 64 sorted queries, one lane per query.  What a lane keeps
+// of the candidates it meets is its searcher, a struct in registers whose members are all inlined:
+//   bool load(long long j)                    reads query j's own arguments; false: it can have no answer
+//   void reset()                              nothing met yet
+//   void eval(float4 q, float4 c)             meets candidate c {x, y, z, bits(row)}
+//   uint32_t bound(bool active, bool& live)   bits of an upper bound of every distance that can still change
+//                                             the lane's answer; live: one can (active, for all but the radius)
+//   void store(long long j), store_none(long long j)
+//   kUnrollSeed                               the form of the seed loop, measured per searcher
+//   kCanFinish                                whether an active lane can stop being live
+// The walk is the same for all: every branch around a ballot, a readlane, a readfirstlane or the wave barrier
+// is wave-uniform, and no lane returns alone before the last of them.
+template <class Searcher>
+__device__ __forceinline__ void lane_walk(Searcher& sr, const IndexView& ix, const float* __restrict__ queries, long long Q,
+                                          const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
+                                          uint32_t* __restrict__ hard, Counters* __restrict__ counters)
 {
     __shared__ uint32_t s_list[kWaves][kListCap];
     const int wave = threadIdx.x / kWave;
@@ -379,10 +393,13 @@ __global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, cons
         inq = j < Q;  // a permutation of [0, Q) by construction
     }
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (inq) q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
-    const bool active = inq && finite3(q.x, q.y, q.z);
-    uint64_t best = ~0ull;
-    if (inq && !active) store_result(best, j, idx_out, dist2_out);
+    bool reach = false;
+    if (inq) {
+        q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
+        reach = sr.load(j);
+    }
+    const bool active = inq && reach && finite3(q.x, q.y, q.z);
+    if (inq && !active) sr.store_none(j);
     if (!__ballot(active)) return;
 
     const long long P = ix.P, nleaves = ix.nleaves;
@@ -396,30 +413,39 @@ __global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, cons
             return;
         }
     }
+    sr.reset();
     // seed: the leaf of the wave's median key and its two Morton neighbours, every point against every lane
     const long long Ls = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave / 2, Q - 1)], lane);
     for (long long C = max(Ls - 1, 0ll); C <= min(Ls + 1, nleaves - 1); C++) {
         const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
-        const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
+        const int nc = (int)min((long long)kLeaf, P - C * kLeaf);  // wave-uniform
+        if constexpr (Searcher::kUnrollSeed) {
 #pragma unroll 16
-        for (int k = 0; k < kLeaf; k++)
-            if (k < nc) eval_lane(pt, k, q, best);  // wave-uniform
+            for (int c = 0; c < kLeaf; c++)
+                if (c < nc) sr.eval(q, lane_point(pt, c));
+        } else {
+            for (int c = 0; c < nc; c++) sr.eval(q, lane_point(pt, c));
+        }
     }
 
-    // the wave's query AABB and the largest lane bound: the coarse filter
+    // the wave's query AABB and the largest bound of its live lanes: the coarse filter
     const float4 qlo = make_float4(wave_min(active ? q.x : FLT_MAX), wave_min(active ? q.y : FLT_MAX),
                                    wave_min(active ? q.z : FLT_MAX), 0.f);
     const float4 qhi = make_float4(wave_max(active ? q.x : -FLT_MAX), wave_max(active ? q.y : -FLT_MAX),
                                    wave_max(active ? q.z : -FLT_MAX), 0.f);
-    uint32_t ub = wave_max_u32(active ? bound_bits(best) : 0u);
+    bool live;
+    uint32_t ub = sr.bound(active, live);
+    ub = wave_max_u32(live ? ub : 0u);
 
     uint32_t* list = s_list[wave];
     int nlist = 0;
     bool bail = false;
-    for (int s0 = 0; s0 < ix.nsuper && !bail; s0 += kWave) {  // one super-box per lane
+    // every lane finished by its seed: no walk (the ballot is left out where live is active, which some lane is)
+    const int nsuper = !Searcher::kCanFinish || __ballot(live) ? ix.nsuper : 0;
+    for (int s0 = 0; s0 < nsuper && !bail; s0 += kWave) {  // one super-box per lane
         const int sidx = s0 + lane;
         bool pass = false;
-        if (sidx < ix.nsuper) pass = box_box_lb(ix.supers[sidx], qlo, qhi) <= ub;
+        if (sidx < nsuper) pass = box_box_lb(ix.supers[sidx], qlo, qhi) <= ub;
         uint64_t smask = __ballot(pass);
         while (smask) {
             const int S = s0 + __builtin_ctzll(smask);
@@ -441,8 +467,9 @@ __global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, cons
         }
     }
     if (bail) {
-        // The wave's queries are spread too far for one coarse filter (queries far outside the cloud, or on
-        // both sides of a Morton jump): phase 2 searches each with its own seed and bound.
+        // The wave's queries are spread too far for one coarse filter (queries far outside the cloud, on both
+        // sides of a Morton jump, or with a large radius): phase 2 searches each again from nothing, with its
+        // own seed and bound.
         push_hard(active, s, lane, hard, counters);
         return;
     }
@@ -450,23 +477,55 @@ __global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, cons
     for (int i = 0; i < nlist; i++) {
         const long long C = (long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)list[i]);
         const Box lb = ix.leaves[C];  // wave-uniform address
-        // fine filter: some lane's own bound reaches the leaf
-        if (!__ballot(active && box_point_lb(lb, q) <= bound_bits(best))) continue;
+        // fine filter: some live lane's own bound reaches the leaf
+        const uint32_t bound = sr.bound(active, live);
+        if (!__ballot(live && box_point_lb(lb, q) <= bound)) continue;
         const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
         const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
-        // a point is evaluated if it is a candidate within the largest lane bound of the query AABB
+        // a point is evaluated if it is a candidate within the largest live bound of the query AABB
         uint64_t pm = __ballot(lane < nc && pt.x == pt.x && box_point_lb(Box{qlo, qhi}, pt) <= ub);
         while (pm) {
-            const int k = __builtin_ctzll(pm);
+            const int c = __builtin_ctzll(pm);
             pm &= pm - 1;
-            eval_lane(pt, k, q, best);
+            sr.eval(q, lane_point(pt, c));
         }
-        ub = wave_max_u32(active ? bound_bits(best) : 0u);
+        const uint32_t after = sr.bound(active, live);
+        ub = wave_max_u32(live ? after : 0u);
     }
-    if (active) store_result(best, j, idx_out, dist2_out);
+    if (active) sr.store(j);
 }
 
-// Phase 2: one wave per hard query; lane c holds candidate c of a leaf.
+// The searcher of the nearest point: one u64 kept by an unsigned min.
+struct LaneBest {
+    static constexpr bool kUnrollSeed = true, kCanFinish = false;
+    int32_t* idx_out;
+    float* dist2_out;
+    uint64_t best = ~0ull;
+
+    __device__ __forceinline__ bool load(long long) { return true; }
+    __device__ __forceinline__ void reset() { best = ~0ull; }
+    __device__ __forceinline__ void eval(float4 q, float4 c) { best = min(best, pack(sqdist(q, c), c.w)); }
+    __device__ __forceinline__ uint32_t bound(bool active, bool& live) const
+    {
+        live = active;
+        return bound_bits(best);
+    }
+    __device__ __forceinline__ void store(long long j) const { store_result(best, j, idx_out, dist2_out); }
+    __device__ __forceinline__ void store_none(long long j) const { store_result(~0ull, j, idx_out, dist2_out); }
+};
+
+__global__ __launch_bounds__(kBlock) void nearest_wave_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
+                                                              const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
+                                                              int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
+                                                              uint32_t* __restrict__ hard, Counters* __restrict__ counters)
+{
+    LaneBest sr{idx_out, dist2_out};
+    lane_walk(sr, ix, queries, Q, qkeys, qorder, hard, counters);
+}
+
+// ---- query: one wave per query of the hard list -------------------------------------------------------
+// Phase 2 of the nearest point: lane c holds candidate c of a leaf and keeps a minimum of its own, reduced once
+// per super-box (the list queries' insertion, nearest_k.h, is another search: DESIGN.md has the measurement).
 __global__ __launch_bounds__(kBlock) void nearest_hard_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
                                                               const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
                                                               int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
@@ -608,6 +667,87 @@ bool overlap(const void* a, size_t na, const void* b, size_t nb)
 
 bool in_range(long long n) { return n >= 0 && n <= kNearestMax; }
 
+// A caller's buffer as the argument checks name it.  `required`: NULL is an error, reported as "NULL <name>"
+// followed by this text.
+struct Span {
+    const void* p;
+    size_t n;
+    const char* name;
+    const char* required = nullptr;
+};
+
+// A query whose arguments passed, keyed and sorted: what its kernels are launched with.
+struct QueryCall {
+    int rc = 0;  // of a call that is over: an error, or nothing left to do
+    hipStream_t s;
+    unsigned nb;  // workgroups of a thread per query; in a lane kernel, of a wave per 64 sorted queries
+    IndexView ix;
+    QueryLayout l;
+};
+
+// What every query of the index does before its own kernels, in the order the errors are documented in: the
+// argument checks (`own_error`: the entry point's verdict on the arguments only it has, reported after k's), the
+// answer of an empty cloud (launched by `none`), the query keys and their sort.  False: the call is over with
+// c.rc.  No host synchronisation and no allocation: it runs under graph capture.
+template <class None>
+bool begin_query(QueryCall& c, const char* name, void* stream, const void* index, size_t index_bytes, long long P,
+                 void* scratch, size_t scratch_bytes, const float* queries, long long Q, int k, int kmin, int kmax,
+                 const char* own_error, std::initializer_list<Span> more_inputs, std::initializer_list<Span> outputs, None none)
+{
+    const std::string who = std::string(name) + ": ";
+    const auto over = [&](int rc) {
+        c.rc = rc;
+        return false;
+    };
+    c.s = as_stream(stream);
+    if (int rc = take_async_error(("hidegs_" + std::string(name)).c_str(), c.s)) return over(rc);
+    if (k < kmin || k > kmax)
+        return over(fail(HIDEGS_E_ARG, who + "k must be in [" + std::to_string(kmin) + ", " + std::to_string(kmax) + "]"));
+    if (own_error) return over(fail(HIDEGS_E_ARG, who + own_error));
+    if (!in_range(P)) return over(fail(HIDEGS_E_ARG, who + "P must be in [0, 2^31)"));
+    if (!in_range(Q)) return over(fail(HIDEGS_E_ARG, who + "Q must be in [0, 2^31)"));
+    if (Q == 0) return over(0);
+    const std::initializer_list<Span> first = {{queries, (size_t)Q * 12, "queries", ""}};
+    for (const auto& list : {first, more_inputs, outputs})
+        for (const Span& b : list)
+            if (b.required && !b.p) return over(fail(HIDEGS_E_ARG, who + "NULL " + b.name + b.required));
+    if (P > 0) {
+        if (!index || !aligned16(index) || index_bytes < index_layout(nullptr, P).total)
+            return over(fail(HIDEGS_E_ARG, who + "index buffer NULL, not 16-byte aligned or too small for P"));
+        if (!scratch || !aligned16(scratch) || scratch_bytes < query_layout(nullptr, Q).total)
+            return over(fail(HIDEGS_E_ARG, who + "scratch buffer NULL, not 16-byte aligned or too small"));
+    } else {
+        index = nullptr, index_bytes = 0, scratch = nullptr, scratch_bytes = 0;  // not used
+    }
+    const std::initializer_list<Span> own = {{index, index_bytes, "the index"}, {scratch, scratch_bytes, "scratch"}};
+    for (const auto& inputs : {first, more_inputs, own})
+        for (const Span& in : inputs)
+            for (const Span& out : outputs)
+                if (overlap(out.p, out.n, in.p, in.n)) return over(fail(HIDEGS_E_ARG, who + out.name + " overlaps " + in.name));
+    for (const Span* a = outputs.begin(); a != outputs.end(); a++)
+        for (const Span* b = a + 1; b != outputs.end(); b++)
+            if (overlap(a->p, a->n, b->p, b->n)) return over(fail(HIDEGS_E_ARG, who + b->name + " overlaps " + a->name));
+    c.nb = (unsigned)ceil_div(Q, kBlock);
+    if (P == 0) {
+        none(c);
+        return over(check_launch(name, c.s, 0));
+    }
+    const IndexLayout il = index_layout(const_cast<void*>(index), P);
+    c.ix = IndexView{il.frame, il.sp, il.leaves, il.supers, il.leaf_keys, P, il.nleaves, il.nsuper};
+    c.l = query_layout(scratch, Q);
+    if (hipMemsetAsync(c.l.counters, 0, sizeof(Counters), c.s) != hipSuccess)
+        return over(fail(HIDEGS_E_HIP, who + "clearing the counter failed"));
+    HIDEGS_LAUNCH("nearest_query_keys", nearest_query_keys_kernel, dim3(c.nb), dim3(kBlock), 0, c.s, queries, Q, c.ix.frame,
+                  c.l.sort.keys, c.l.sort.vals);
+    if (int rc = sort_pairs_u64(c.l.sort.sort_tmp, c.l.sort.sort_bytes, c.l.sort.keys, c.l.sort.keys_sorted, c.l.sort.vals,
+                                c.l.sort.vals_sorted, Q, 0, 3 * kMortonBits, c.s))
+        return over(rc);
+    return true;
+}
+
+// The grid of a wave-per-query launch: a wave per query up to kHardGrid workgroups, whose waves stride on.
+dim3 hard_grid(long long Q) { return dim3(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves))); }
+
 #include "nearest_k.h"
 #include "nearest_within.h"
 
@@ -667,57 +807,18 @@ extern "C" int hidegs_nearest_query(const void* index, size_t index_bytes, long 
                                     float* dist2_out, void* stream)
 {
     using namespace hidegs;
-    hipStream_t s = as_stream(stream);
-    if (int rc = take_async_error("hidegs_nearest_query", s)) return rc;
-    if (!in_range(P)) return fail(HIDEGS_E_ARG, "nearest_query: P must be in [0, 2^31)");
-    if (!in_range(Q)) return fail(HIDEGS_E_ARG, "nearest_query: Q must be in [0, 2^31)");
-    if (Q == 0) return 0;
-    if (!queries) return fail(HIDEGS_E_ARG, "nearest_query: NULL queries");
-    if (!idx_out) return fail(HIDEGS_E_ARG, "nearest_query: NULL idx_out");
-    if (!dist2_out) return fail(HIDEGS_E_ARG, "nearest_query: NULL dist2_out");
-    if (P > 0) {
-        if (!index || !aligned16(index) || index_bytes < index_layout(nullptr, P).total)
-            return fail(HIDEGS_E_ARG, "nearest_query: index buffer NULL, not 16-byte aligned or too small for P");
-        if (!scratch || !aligned16(scratch) || scratch_bytes < query_layout(nullptr, Q).total)
-            return fail(HIDEGS_E_ARG, "nearest_query: scratch buffer NULL, not 16-byte aligned or too small");
-    } else {
-        index = nullptr, index_bytes = 0, scratch = nullptr, scratch_bytes = 0;  // not used
-    }
     const size_t out_bytes = (size_t)Q * 4;
-    struct {
-        const void* p;
-        size_t n;
-        const char* name;
-    } const inputs[] = {{queries, (size_t)Q * 12, "queries"}, {index, index_bytes, "the index"}, {scratch, scratch_bytes, "scratch"}};
-    for (const auto& in : inputs) {
-        if (overlap(idx_out, out_bytes, in.p, in.n))
-            return fail(HIDEGS_E_ARG, std::string("nearest_query: idx_out overlaps ") + in.name);
-        if (overlap(dist2_out, out_bytes, in.p, in.n))
-            return fail(HIDEGS_E_ARG, std::string("nearest_query: dist2_out overlaps ") + in.name);
-    }
-    if (overlap(idx_out, out_bytes, dist2_out, out_bytes)) return fail(HIDEGS_E_ARG, "nearest_query: dist2_out overlaps idx_out");
-    const unsigned nb = (unsigned)ceil_div(Q, kBlock);
-    if (P == 0) {
-        HIDEGS_LAUNCH("nearest_none", nearest_none_kernel, dim3(nb), dim3(kBlock), 0, s, Q, idx_out, dist2_out);
-        return check_launch("nearest_query", s, 0);
-    }
-    const IndexLayout il = index_layout(const_cast<void*>(index), P);
-    const IndexView ix{il.frame, il.sp, il.leaves, il.supers, il.leaf_keys, P, il.nleaves, il.nsuper};
-    const QueryLayout l = query_layout(scratch, Q);
-    if (hipMemsetAsync(l.counters, 0, sizeof(Counters), s) != hipSuccess)
-        return fail(HIDEGS_E_HIP, "nearest_query: clearing the counter failed");
-    HIDEGS_LAUNCH("nearest_query_keys", nearest_query_keys_kernel, dim3(nb), dim3(kBlock), 0, s, queries, Q, ix.frame,
-                  l.sort.keys, l.sort.vals);
-    if (int rc = sort_pairs_u64(l.sort.sort_tmp, l.sort.sort_bytes, l.sort.keys, l.sort.keys_sorted, l.sort.vals,
-                                l.sort.vals_sorted, Q, 0, 3 * kMortonBits, s))
-        return rc;
-    const unsigned nwg = (unsigned)ceil_div(Q, kBlock);  // one wave per 64 sorted queries
-    HIDEGS_LAUNCH("nearest_wave", nearest_wave_kernel, dim3(nwg), dim3(kBlock), 0, s, ix, queries, Q, l.sort.keys_sorted,
-                  l.sort.vals_sorted, idx_out, dist2_out, l.hard, l.counters);
-    HIDEGS_LAUNCH("nearest_hard", nearest_hard_kernel, dim3(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves))),
-                  dim3(kBlock), 0, s, ix, queries, Q, l.sort.keys_sorted, l.sort.vals_sorted, idx_out, dist2_out, l.hard,
-                  l.counters);
-    return check_launch("nearest_query", s, 0);
+    QueryCall c;
+    if (!begin_query(c, "nearest_query", stream, index, index_bytes, P, scratch, scratch_bytes, queries, Q, 1, 1, 1, nullptr, {},
+                     {{idx_out, out_bytes, "idx_out", ""}, {dist2_out, out_bytes, "dist2_out", ""}}, [&](const QueryCall& c) {
+                         HIDEGS_LAUNCH("nearest_none", nearest_none_kernel, dim3(c.nb), dim3(kBlock), 0, c.s, Q, idx_out, dist2_out);
+                     }))
+        return c.rc;
+    HIDEGS_LAUNCH("nearest_wave", nearest_wave_kernel, dim3(c.nb), dim3(kBlock), 0, c.s, c.ix, queries, Q, c.l.sort.keys_sorted,
+                  c.l.sort.vals_sorted, idx_out, dist2_out, c.l.hard, c.l.counters);
+    HIDEGS_LAUNCH("nearest_hard", nearest_hard_kernel, hard_grid(Q), dim3(kBlock), 0, c.s, c.ix, queries, Q, c.l.sort.keys_sorted,
+                  c.l.sort.vals_sorted, idx_out, dist2_out, c.l.hard, c.l.counters);
+    return check_launch("nearest_query", c.s, 0);
 }
 
 extern "C" size_t hidegs_nearest_query_k_scratch_bytes(long long P, long long Q, int k)

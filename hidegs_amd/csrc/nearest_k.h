@@ -1,7 +1,7 @@
 // nearest_k.h -- the k-nearest query of the nearest-point index (include/hidegs_nearest_k.h): a stage of
 // nearest.hip, included inside its namespace.  The index, the query keys, the Morton sort of the queries, the
-// lower bounds and the hard list are nearest.hip's; what is new is that every searcher keeps its k best
-// instead of its best, and that every filter takes its bound from the k-th best.
+// lower bounds, the hard list and the lane walk are nearest.hip's; what is new is that every searcher keeps its
+// k best instead of its best, and that every filter takes its bound from the k-th best.
 //
 // A candidate is one u64, bits(d) << 32 | row: the contract's order is the unsigned order of these values, and
 // a slot that holds nothing is ~0.  The excluded row is given ~0 where its value is formed, so it can enter no
@@ -13,14 +13,16 @@
 // bound is +inf.  Each point is evaluated at most once per query (the seed leaves are left out of the walk and
 // a leaf is listed once), so a list never holds a row twice.
 //
-//   nearest_k_wave_kernel<K>: nearest_wave_kernel's walk, one lane per sorted query; the lane's K best are a
+//   LaneK<K>, the searcher of nearest_k_wave_kernel<K> (nearest.hip's lane_walk): the lane's K best are a
 //     sorted array in registers (static indices only).  A call with k <= K keeps K - k slots at 0 below the
 //     list: nothing is below 0, so they stay, the list's last entry is the k-th best whatever k is, and the
 //     k results are the last k slots.
-//   nearest_k_route_kernel: for k above kLaneKMax, sends every finite query to the hard list.
-//   nearest_k_hard_kernel: one wave per query of the hard list; lane i holds the i-th best.
+//   nearest_route_kernel<Searcher>: for k above kLaneKMax, sends every query that can have an answer to the
+//     hard list.
+//   hard_list_walk<RADIUS, LIST>: one wave per query of the hard list; lane i holds the i-th best.  With
+//     RADIUS it is the fixed-radius query's as well (nearest_within.h), which counts and keeps what is in range.
 
-constexpr int kLaneKMax = 16;  // the largest K of nearest_k_wave_kernel: instantiated for 4, 8 and 16
+constexpr int kLaneKMax = 16;  // the largest K of a lane's list: instantiated for 4, 8 and 16
 constexpr int kNearestKMax = 64;
 static_assert(kNearestKMax <= kWave, "the hard path holds one of the k best per lane");
 
@@ -51,6 +53,16 @@ __device__ __forceinline__ uint32_t excluded_row(const int32_t* __restrict__ exc
     return exclude ? (uint32_t)exclude[j] : 0xffffffffu;
 }
 
+// The radius rule (nearest_within.h): rb, the bits of a squared radius, and whether anything can be in range
+// of it at all.  For r2 >= 0 clearing the sign bit is r2 + 0.0f: -0 is 0.
+__device__ __forceinline__ bool radius_bits(float r2, uint32_t& rb)
+{
+    rb = __float_as_uint(r2) & 0x7fffffffu;
+    return r2 >= 0.f;  // false for a NaN
+}
+
+__device__ __forceinline__ bool in_reach(uint64_t v, uint32_t rb) { return (uint32_t)(v >> 32) <= rb; }
+
 // list is ascending and v < list[K - 1]: v takes its place, the last entry leaves.
 template <int K>
 __device__ __forceinline__ void insert_k(uint64_t (&list)[K], uint64_t v)
@@ -60,19 +72,48 @@ __device__ __forceinline__ void insert_k(uint64_t (&list)[K], uint64_t v)
     list[0] = min(v, list[0]);
 }
 
-// The list against the point held by lane c of `pt`, broadcast to every lane.
+// The searcher of the k nearest (k <= K, wave-uniform).
 template <int K>
-__device__ __forceinline__ void eval_lane_k(float4 pt, int c, float4 q, uint32_t excl, uint64_t (&list)[K])
-{
-    const float4 p = make_float4(uniform_lane(pt.x, c), uniform_lane(pt.y, c), uniform_lane(pt.z, c), uniform_lane(pt.w, c));
-    const uint64_t v = pack_unless(q, p, excl);
-    if (v < list[K - 1]) insert_k(list, v);
-}
+struct LaneK {
+    static constexpr bool kUnrollSeed = false, kCanFinish = false;
+    int k;
+    const int32_t* exclude;
+    int32_t* idx_out;
+    float* dist2_out;
+    uint32_t excl = 0xffffffffu;
+    uint64_t list[K];  // ascending; list[K - 1] is the k-th best
 
-__device__ __forceinline__ void store_none_k(long long j, int k, int32_t* __restrict__ idx_out, float* __restrict__ dist2_out)
-{
-    for (int i = 0; i < k; i++) store_result(~0ull, j * k + i, idx_out, dist2_out);
-}
+    __device__ __forceinline__ bool load(long long j)
+    {
+        excl = excluded_row(exclude, j);
+        return true;
+    }
+    __device__ __forceinline__ void reset()
+    {
+#pragma unroll
+        for (int i = 0; i < K; i++) list[i] = i < K - k ? 0ull : ~0ull;
+    }
+    __device__ __forceinline__ void eval(float4 q, float4 c)
+    {
+        const uint64_t v = pack_unless(q, c, excl);
+        if (v < list[K - 1]) insert_k(list, v);
+    }
+    __device__ __forceinline__ uint32_t bound(bool active, bool& live) const
+    {
+        live = active;
+        return bound_bits(list[K - 1]);
+    }
+    __device__ __forceinline__ void store(long long j) const
+    {
+#pragma unroll
+        for (int i = 0; i < K; i++)
+            if (i >= K - k) store_result(list[i], j * k + (i - (K - k)), idx_out, dist2_out);
+    }
+    __device__ __forceinline__ void store_none(long long j) const
+    {
+        for (int i = 0; i < k; i++) store_result(~0ull, j * k + i, idx_out, dist2_out);
+    }
+};
 
 template <int K>
 __global__ __launch_bounds__(kBlock) void nearest_k_wave_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
@@ -82,117 +123,16 @@ __global__ __launch_bounds__(kBlock) void nearest_k_wave_kernel(IndexView ix, co
                                                                 float* __restrict__ dist2_out, uint32_t* __restrict__ hard,
                                                                 Counters* __restrict__ counters)
 {
-    __shared__ uint32_t s_list[kWaves][kListCap];
-    const int wave = threadIdx.x / kWave;
-    const int lane = lane_id();
-    const long long base = ((long long)blockIdx.x * kWaves + wave) * kWave;
-    if (base >= Q) return;  // whole wave; no workgroup barrier below
-
-    const long long s = base + lane;
-    long long j = 0;
-    bool inq = s < Q;
-    if (inq) {
-        j = qorder[s];
-        inq = j < Q;  // a permutation of [0, Q) by construction
-    }
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    uint32_t excl = 0xffffffffu;
-    if (inq) {
-        q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
-        excl = excluded_row(exclude, j);
-    }
-    const bool active = inq && finite3(q.x, q.y, q.z);
-    if (inq && !active) store_none_k(j, k, idx_out, dist2_out);
-    if (!__ballot(active)) return;
-
-    const long long P = ix.P, nleaves = ix.nleaves;
-    {
-        const long long lf = find_leaf(ix.leaf_keys, nleaves, qkeys[base], lane);
-        const long long ll = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave - 1, Q - 1)], lane);
-        if (ll - lf > kSpanBail) {
-            push_hard(active, s, lane, hard, counters);
-            return;
-        }
-    }
-    uint64_t list[K];  // ascending; list[K - 1] is the k-th best
-#pragma unroll
-    for (int i = 0; i < K; i++) list[i] = i < K - k ? 0ull : ~0ull;  // k is wave-uniform
-
-    // seed: the leaf of the wave's median key and its two Morton neighbours, every point against every lane
-    const long long Ls = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave / 2, Q - 1)], lane);
-    for (long long C = max(Ls - 1, 0ll); C <= min(Ls + 1, nleaves - 1); C++) {
-        const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
-        const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
-        for (int c = 0; c < nc; c++) eval_lane_k(pt, c, q, excl, list);  // wave-uniform
-    }
-
-    // the wave's query AABB and the largest k-th bound of its lanes: the coarse filter
-    const float4 qlo = make_float4(wave_min(active ? q.x : FLT_MAX), wave_min(active ? q.y : FLT_MAX),
-                                   wave_min(active ? q.z : FLT_MAX), 0.f);
-    const float4 qhi = make_float4(wave_max(active ? q.x : -FLT_MAX), wave_max(active ? q.y : -FLT_MAX),
-                                   wave_max(active ? q.z : -FLT_MAX), 0.f);
-    uint32_t ub = wave_max_u32(active ? bound_bits(list[K - 1]) : 0u);
-
-    uint32_t* cand = s_list[wave];
-    int ncand = 0;
-    bool bail = false;
-    for (int s0 = 0; s0 < ix.nsuper && !bail; s0 += kWave) {  // one super-box per lane
-        const int sidx = s0 + lane;
-        bool pass = false;
-        if (sidx < ix.nsuper) pass = box_box_lb(ix.supers[sidx], qlo, qhi) <= ub;
-        uint64_t smask = __ballot(pass);
-        while (smask) {
-            const int S = s0 + __builtin_ctzll(smask);
-            smask &= smask - 1;
-            const long long l = (long long)S * kFan + lane;
-            bool lpass = false;
-            if (l < nleaves && (l < Ls - 1 || l > Ls + 1))  // those three were the seed
-                lpass = box_box_lb(ix.leaves[l], qlo, qhi) <= ub;
-            const uint64_t lm = __ballot(lpass);
-            const int cnt = __popcll(lm);
-            if (cnt == 0) continue;
-            if (ncand + cnt > kBailout) {
-                bail = true;
-                break;
-            }
-            if (lpass) cand[ncand + __popcll(lm & lanes_below(lane))] = (uint32_t)l;
-            ncand += cnt;
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    if (bail) {
-        push_hard(active, s, lane, hard, counters);
-        return;
-    }
-
-    for (int i = 0; i < ncand; i++) {
-        const long long C = (long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cand[i]);
-        const Box lb = ix.leaves[C];  // wave-uniform address
-        // fine filter: some lane's own k-th bound reaches the leaf
-        if (!__ballot(active && box_point_lb(lb, q) <= bound_bits(list[K - 1]))) continue;
-        const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
-        const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
-        // a point is evaluated if it is a candidate within the largest k-th bound of the query AABB
-        uint64_t pm = __ballot(lane < nc && pt.x == pt.x && box_point_lb(Box{qlo, qhi}, pt) <= ub);
-        while (pm) {
-            const int c = __builtin_ctzll(pm);
-            pm &= pm - 1;
-            eval_lane_k(pt, c, q, excl, list);
-        }
-        ub = wave_max_u32(active ? bound_bits(list[K - 1]) : 0u);
-    }
-    if (active) {
-#pragma unroll
-        for (int i = 0; i < K; i++)
-            if (i >= K - k) store_result(list[i], j * k + (i - (K - k)), idx_out, dist2_out);
-    }
+    LaneK<K> sr{k, exclude, idx_out, dist2_out};
+    lane_walk(sr, ix, queries, Q, qkeys, qorder, hard, counters);
 }
 
-// k above kLaneKMax: a non-finite query is answered here, every other one goes to the hard list.
-__global__ __launch_bounds__(kBlock) void nearest_k_route_kernel(const float* __restrict__ queries, long long Q,
-                                                                 const uint32_t* __restrict__ qorder, int k,
-                                                                 int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
-                                                                 uint32_t* __restrict__ hard, Counters* __restrict__ counters)
+// k above kLaneKMax, a thread per query: one that can have no answer (it is not finite, or its searcher says so)
+// is answered here, every other one goes to the hard list.
+template <class Searcher>
+__global__ __launch_bounds__(kBlock) void nearest_route_kernel(const float* __restrict__ queries, long long Q,
+                                                               const uint32_t* __restrict__ qorder, Searcher sr,
+                                                               uint32_t* __restrict__ hard, Counters* __restrict__ counters)
 {
     const long long s = (long long)blockIdx.x * kBlock + threadIdx.x;
     long long j = 0;
@@ -203,21 +143,26 @@ __global__ __launch_bounds__(kBlock) void nearest_k_route_kernel(const float* __
     }
     bool active = false;
     if (inq) {
-        active = finite3(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2]);
-        if (!active) store_none_k(j, k, idx_out, dist2_out);
+        active = sr.load(j) && finite3(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2]);
+        if (!active) sr.store_none(j);
     }
     push_hard(active, s, lane_id(), hard, counters);
 }
 
-// One wave per hard query.  Lane i holds the i-th best (~0: none yet); kth is lane k - 1's value, the bound
-// of every filter, read again after every insertion.
-__global__ __launch_bounds__(kBlock) void nearest_k_hard_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
-                                                                const uint64_t* __restrict__ qkeys,
-                                                                const uint32_t* __restrict__ qorder, int k,
-                                                                const int32_t* __restrict__ exclude, int32_t* __restrict__ idx_out,
-                                                                float* __restrict__ dist2_out, const uint32_t* __restrict__ hard,
-                                                                const Counters* __restrict__ counters)
+// One wave per hard query, for both list queries.  Lane i holds the i-th best (~0: none yet); kth is lane
+// k - 1's value, read again after every insertion; bnd is the bound of every filter, formed again after every
+// leaf.  With RADIUS only what is in range is kept, count (wave-uniform) is how many were, and bnd follows
+// nearest_within.h's rule; without, bnd is the k-th best's bits.  LIST is k > 0: without it there is no list, kth
+// is 0 (nothing is below it) and a saturated query leaves every loop.
+template <bool RADIUS, bool LIST>
+__device__ __forceinline__ void hard_list_walk(const IndexView& ix, const float* __restrict__ queries, long long Q,
+                                               const uint64_t* __restrict__ qkeys, const uint32_t* __restrict__ qorder,
+                                               const float* __restrict__ r2, int k, uint32_t max_count,
+                                               const int32_t* __restrict__ exclude, int32_t* __restrict__ count_out,
+                                               int32_t* __restrict__ idx_out, float* __restrict__ dist2_out,
+                                               const uint32_t* __restrict__ hard, const Counters* __restrict__ counters)
 {
+    static_assert(RADIUS || LIST, "without a radius there is a list");
     const int lane = lane_id();
     const long long P = ix.P, nleaves = ix.nleaves;
     const uint32_t nhard = min(counters->hard, (uint32_t)Q);
@@ -229,16 +174,28 @@ __global__ __launch_bounds__(kBlock) void nearest_k_hard_kernel(IndexView ix, co
         if (j >= Q) continue;
         const float4 q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
         const uint32_t excl = excluded_row(exclude, j);
+        uint32_t rb = kInfBits;
+        if constexpr (RADIUS)
+            if (!radius_bits(r2[j], rb)) continue;  // never listed: answered by the launch before
         const long long L = find_leaf(ix.leaf_keys, nleaves, qkeys[s], lane);
-        uint64_t top = ~0ull, kth = ~0ull;
+        uint64_t top = ~0ull, kth = LIST ? ~0ull : 0ull;
+        uint32_t count = 0;
+        uint32_t bnd = rb;
+        const auto open = [&] { return LIST || count < max_count; };  // wave-uniform
 
-        // The 64 points of leaf C, one per lane: those below the k-th best are inserted one by one, lowest lane
-        // first.  Its rank is the number of entries below it; the entries from there on move up a lane.
+        // The 64 points of leaf C, one per lane: those to keep (with RADIUS, those in range, which are counted)
+        // that are below the k-th best are inserted one by one, lowest lane first.  A value's rank is the number
+        // of entries below it; the entries from there on move up a lane.
         auto batch = [&](long long C) {
             const long long c = C * kLeaf + lane;
             uint64_t v = ~0ull;
             if (c < P) v = pack_unless(q, ix.sp[c], excl);
-            uint64_t m = __ballot(v < kth);
+            bool keep = true;
+            if constexpr (RADIUS) {
+                keep = in_reach(v, rb);
+                count += (uint32_t)__popcll(__ballot(keep));
+            }
+            uint64_t m = LIST ? __ballot(keep && v < kth) : 0ull;
             while (m) {
                 const int b = __builtin_ctzll(m);
                 m &= m - 1;
@@ -249,31 +206,44 @@ __global__ __launch_bounds__(kBlock) void nearest_k_hard_kernel(IndexView ix, co
                 top = lane > rank ? up : (lane == rank ? cv : top);
                 kth = readlane_u64(top, k - 1);
             }
+            bnd = RADIUS && count < max_count ? rb : bound_bits(kth);
         };
 
         for (long long C = max(L - 1, 0ll); C <= min(L + 1, nleaves - 1); C++) batch(C);
-        for (int s0 = 0; s0 < ix.nsuper; s0 += kWave) {  // one super-box per lane
+        for (int s0 = 0; s0 < ix.nsuper && open(); s0 += kWave) {  // one super-box per lane
             const int sidx = s0 + lane;
             bool pass = false;
-            if (sidx < ix.nsuper) pass = box_point_lb(ix.supers[sidx], q) <= bound_bits(kth);
+            if (sidx < ix.nsuper) pass = box_point_lb(ix.supers[sidx], q) <= bnd;
             uint64_t smask = __ballot(pass);
-            while (smask) {
+            while (smask && open()) {
                 const int S = s0 + __builtin_ctzll(smask);
                 smask &= smask - 1;
                 const long long l = (long long)S * kFan + lane;
                 uint32_t llb = 0xffffffffu;  // above every bound: no leaf, or one of the seed
                 if (l < nleaves && (l < L - 1 || l > L + 1)) llb = box_point_lb(ix.leaves[l], q);
-                uint64_t lmask = __ballot(llb <= bound_bits(kth));
-                while (lmask) {
+                uint64_t lmask = __ballot(llb <= bnd);
+                while (lmask && open()) {
                     const int b = __builtin_ctzll(lmask);
                     lmask &= lmask - 1;
-                    if ((uint32_t)__builtin_amdgcn_readlane((int)llb, b) > bound_bits(kth)) continue;
+                    if ((uint32_t)__builtin_amdgcn_readlane((int)llb, b) > bnd) continue;  // it has come down since
                     batch((long long)S * kFan + b);
                 }
             }
         }
-        if (lane < k) store_result(top, j * k + lane, idx_out, dist2_out);
+        if constexpr (RADIUS)
+            if (lane == 0) count_out[j] = (int32_t)min(count, max_count);
+        if (LIST && lane < k) store_result(top, j * k + lane, idx_out, dist2_out);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void nearest_k_hard_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
+                                                                const uint64_t* __restrict__ qkeys,
+                                                                const uint32_t* __restrict__ qorder, int k,
+                                                                const int32_t* __restrict__ exclude, int32_t* __restrict__ idx_out,
+                                                                float* __restrict__ dist2_out, const uint32_t* __restrict__ hard,
+                                                                const Counters* __restrict__ counters)
+{
+    hard_list_walk<false, true>(ix, queries, Q, qkeys, qorder, nullptr, k, 0u, exclude, nullptr, idx_out, dist2_out, hard, counters);
 }
 
 // The query scratch is nearest_query's: the counter word, the (key, row) sort, the hard list.
@@ -283,78 +253,36 @@ size_t query_k_scratch_bytes(long long P, long long Q, int k)
 }
 
 template <int K>
-void launch_k_wave(hipStream_t s, unsigned nwg, const IndexView& ix, const float* queries, long long Q, const QueryLayout& l,
-                   int k, const int32_t* exclude, int32_t* idx_out, float* dist2_out)
+void launch_k_wave(const QueryCall& c, const float* queries, long long Q, int k, const int32_t* exclude, int32_t* idx_out,
+                   float* dist2_out)
 {
-    HIDEGS_LAUNCH("nearest_k_wave", nearest_k_wave_kernel<K>, dim3(nwg), dim3(kBlock), 0, s, ix, queries, Q,
-                  l.sort.keys_sorted, l.sort.vals_sorted, k, exclude, idx_out, dist2_out, l.hard, l.counters);
+    HIDEGS_LAUNCH("nearest_k_wave", nearest_k_wave_kernel<K>, dim3(c.nb), dim3(kBlock), 0, c.s, c.ix, queries, Q,
+                  c.l.sort.keys_sorted, c.l.sort.vals_sorted, k, exclude, idx_out, dist2_out, c.l.hard, c.l.counters);
 }
 
 int query_k(const void* index, size_t index_bytes, long long P, void* scratch, size_t scratch_bytes, const float* queries,
             long long Q, int k, const int32_t* exclude, int32_t* idx_out, float* dist2_out, void* stream)
 {
-    hipStream_t s = as_stream(stream);
-    if (int rc = take_async_error("hidegs_nearest_query_k", s)) return rc;
-    if (k < 1 || k > kNearestKMax) return fail(HIDEGS_E_ARG, "nearest_query_k: k must be in [1, 64]");
-    if (!in_range(P)) return fail(HIDEGS_E_ARG, "nearest_query_k: P must be in [0, 2^31)");
-    if (!in_range(Q)) return fail(HIDEGS_E_ARG, "nearest_query_k: Q must be in [0, 2^31)");
-    if (Q == 0) return 0;
-    if (!queries) return fail(HIDEGS_E_ARG, "nearest_query_k: NULL queries");
-    if (!idx_out) return fail(HIDEGS_E_ARG, "nearest_query_k: NULL idx_out");
-    if (!dist2_out) return fail(HIDEGS_E_ARG, "nearest_query_k: NULL dist2_out");
-    if (P > 0) {
-        if (!index || !aligned16(index) || index_bytes < index_layout(nullptr, P).total)
-            return fail(HIDEGS_E_ARG, "nearest_query_k: index buffer NULL, not 16-byte aligned or too small for P");
-        if (!scratch || !aligned16(scratch) || scratch_bytes < query_layout(nullptr, Q).total)
-            return fail(HIDEGS_E_ARG, "nearest_query_k: scratch buffer NULL, not 16-byte aligned or too small");
-    } else {
-        index = nullptr, index_bytes = 0, scratch = nullptr, scratch_bytes = 0;  // not used
-    }
     const size_t out_bytes = (size_t)Q * (size_t)k * 4;
-    struct {
-        const void* p;
-        size_t n;
-        const char* name;
-    } const inputs[] = {{queries, (size_t)Q * 12, "queries"},
-                        {exclude, (size_t)Q * 4, "exclude"},
-                        {index, index_bytes, "the index"},
-                        {scratch, scratch_bytes, "scratch"}};
-    for (const auto& in : inputs) {
-        if (overlap(idx_out, out_bytes, in.p, in.n))
-            return fail(HIDEGS_E_ARG, std::string("nearest_query_k: idx_out overlaps ") + in.name);
-        if (overlap(dist2_out, out_bytes, in.p, in.n))
-            return fail(HIDEGS_E_ARG, std::string("nearest_query_k: dist2_out overlaps ") + in.name);
-    }
-    if (overlap(idx_out, out_bytes, dist2_out, out_bytes))
-        return fail(HIDEGS_E_ARG, "nearest_query_k: dist2_out overlaps idx_out");
-    if (P == 0) {
-        const long long n = Q * k;
-        HIDEGS_LAUNCH("nearest_none", nearest_none_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0, s, n, idx_out,
-                      dist2_out);
-        return check_launch("nearest_query_k", s, 0);
-    }
-    const IndexLayout il = index_layout(const_cast<void*>(index), P);
-    const IndexView ix{il.frame, il.sp, il.leaves, il.supers, il.leaf_keys, P, il.nleaves, il.nsuper};
-    const QueryLayout l = query_layout(scratch, Q);
-    if (hipMemsetAsync(l.counters, 0, sizeof(Counters), s) != hipSuccess)
-        return fail(HIDEGS_E_HIP, "nearest_query_k: clearing the counter failed");
-    const unsigned nb = (unsigned)ceil_div(Q, kBlock);  // a thread per query; in the wave kernel, a wave per 64 sorted queries
-    HIDEGS_LAUNCH("nearest_query_keys", nearest_query_keys_kernel, dim3(nb), dim3(kBlock), 0, s, queries, Q, ix.frame,
-                  l.sort.keys, l.sort.vals);
-    if (int rc = sort_pairs_u64(l.sort.sort_tmp, l.sort.sort_bytes, l.sort.keys, l.sort.keys_sorted, l.sort.vals,
-                                l.sort.vals_sorted, Q, 0, 3 * kMortonBits, s))
-        return rc;
+    QueryCall c;
+    if (!begin_query(c, "nearest_query_k", stream, index, index_bytes, P, scratch, scratch_bytes, queries, Q, k, 1, kNearestKMax,
+                     nullptr, {{exclude, (size_t)Q * 4, "exclude"}},
+                     {{idx_out, out_bytes, "idx_out", ""}, {dist2_out, out_bytes, "dist2_out", ""}}, [&](const QueryCall& c) {
+                         const long long n = Q * k;
+                         HIDEGS_LAUNCH("nearest_none", nearest_none_kernel, dim3((unsigned)ceil_div(n, kBlock)), dim3(kBlock), 0,
+                                       c.s, n, idx_out, dist2_out);
+                     }))
+        return c.rc;
     if (k <= 4)
-        launch_k_wave<4>(s, nb, ix, queries, Q, l, k, exclude, idx_out, dist2_out);
+        launch_k_wave<4>(c, queries, Q, k, exclude, idx_out, dist2_out);
     else if (k <= 8)
-        launch_k_wave<8>(s, nb, ix, queries, Q, l, k, exclude, idx_out, dist2_out);
+        launch_k_wave<8>(c, queries, Q, k, exclude, idx_out, dist2_out);
     else if (k <= kLaneKMax)
-        launch_k_wave<kLaneKMax>(s, nb, ix, queries, Q, l, k, exclude, idx_out, dist2_out);
+        launch_k_wave<kLaneKMax>(c, queries, Q, k, exclude, idx_out, dist2_out);
     else
-        HIDEGS_LAUNCH("nearest_k_route", nearest_k_route_kernel, dim3(nb), dim3(kBlock), 0, s, queries, Q, l.sort.vals_sorted, k,
-                      idx_out, dist2_out, l.hard, l.counters);
-    HIDEGS_LAUNCH("nearest_k_hard", nearest_k_hard_kernel, dim3(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves))),
-                  dim3(kBlock), 0, s, ix, queries, Q, l.sort.keys_sorted, l.sort.vals_sorted, k, exclude, idx_out, dist2_out,
-                  l.hard, l.counters);
-    return check_launch("nearest_query_k", s, 0);
+        HIDEGS_LAUNCH("nearest_k_route", nearest_route_kernel<LaneK<1>>, dim3(c.nb), dim3(kBlock), 0, c.s, queries, Q,
+                      c.l.sort.vals_sorted, LaneK<1>{k, exclude, idx_out, dist2_out}, c.l.hard, c.l.counters);
+    HIDEGS_LAUNCH("nearest_k_hard", nearest_k_hard_kernel, hard_grid(Q), dim3(kBlock), 0, c.s, c.ix, queries, Q,
+                  c.l.sort.keys_sorted, c.l.sort.vals_sorted, k, exclude, idx_out, dist2_out, c.l.hard, c.l.counters);
+    return check_launch("nearest_query_k", c.s, 0);
 }

@@ -1,8 +1,9 @@
 // nearest_within.h -- the fixed-radius query of the nearest-point index (include/hidegs_nearest_within.h): a
 // stage of nearest.hip, included inside its namespace after nearest_k.h.  The index, the query keys, the Morton
-// sort of the queries, the lower bounds, the hard list and the u64 candidates are nearest.hip's and
-// nearest_k.h's; what is new is that every searcher counts the candidates within its query's radius, keeps the
-// k best of those only, and takes the bound of every filter from one rule.
+// sort of the queries, the lower bounds, the hard list and the lane walk are nearest.hip's, the u64 candidates,
+// the route kernel and the wave-per-query walk nearest_k.h's; what is new is that every searcher counts the
+// candidates within its query's radius, keeps the k best of those only, and takes the bound of every filter from
+// one rule.
 //
 // In range: bits(d) <= rb, the bits of the query's squared radius (the excluded row's ~0 and a non-candidate's
 // NaN are above every rb).  A query whose radius is negative or a NaN is answered where a non-finite query is.
@@ -18,28 +19,62 @@
 // leaf is listed once): the count is exact.  After saturation the count is max_count by definition and
 // nearest_k.h's k-th-best argument covers the list.  Seeds, order and bail-outs change the speed only.
 //
-//   nearest_within_wave_kernel<K>, K = 0, 4, 8, 16: nearest_k_wave_kernel's walk, one lane per sorted query,
-//     with a count per lane.  K = 0 keeps no list.  A large radius makes most waves bail: they hand their
-//     queries to the hard list, as intended.
-//   nearest_within_route_kernel: for k above kLaneKMax, sends every query that can have an answer there.
-//   nearest_within_hard_kernel: one wave per query of the hard list; lane i holds the i-th best, the count is
-//     wave-uniform.
+//   LaneWithin<K>, K = 0, 4, 8, 16, the searcher of nearest_within_wave_kernel<K> (nearest.hip's lane_walk):
+//     LaneK's list with a count per lane.  K = 0 keeps no list.  A large radius makes most waves bail: they hand
+//     their queries to the hard list, as intended.
+//   nearest_within_wave_own_kernel<16>: K = 16 runs lane_walk's text written out, for its registers (see there).
+//   nearest_within_hard_kernel<LIST>: nearest_k.h's hard_list_walk with the radius.
 
-// rb and whether anything can be in range at all.  For r2 >= 0 clearing the sign bit is r2 + 0.0f: -0 is 0.
-__device__ __forceinline__ bool radius_bits(float r2, uint32_t& rb)
-{
-    rb = __float_as_uint(r2) & 0x7fffffffu;
-    return r2 >= 0.f;  // false for a NaN
-}
+// The searcher of the count within a radius and of the k nearest of those (k <= K, wave-uniform).
+template <int K>
+struct LaneWithin {
+    static constexpr bool kUnrollSeed = false, kCanFinish = true;
+    LaneK<(K ? K : 1)> in;  // the k best in range; at K = 0 only its arguments
+    const float* r2;
+    uint32_t max_count;
+    int32_t* count_out;
+    uint32_t rb = 0, count = 0;
 
-__device__ __forceinline__ bool in_reach(uint64_t v, uint32_t rb) { return (uint32_t)(v >> 32) <= rb; }
-
-__device__ __forceinline__ void store_none_within(long long j, int k, int32_t* __restrict__ count_out,
-                                                  int32_t* __restrict__ idx_out, float* __restrict__ dist2_out)
-{
-    count_out[j] = 0;
-    store_none_k(j, k, idx_out, dist2_out);
-}
+    __device__ __forceinline__ bool load(long long j)
+    {
+        in.load(j);
+        return radius_bits(r2[j], rb);
+    }
+    __device__ __forceinline__ void reset()
+    {
+        count = 0;
+        if constexpr (K > 0) in.reset();
+    }
+    __device__ __forceinline__ void eval(float4 q, float4 c)
+    {
+        uint64_t v = pack_unless(q, c, in.excl);
+        const bool reach = in_reach(v, rb);
+        count += reach;  // at most once per point: below 2^31
+        if constexpr (K > 0) {
+            v = reach ? v : ~0ull;  // out of range: below no entry
+            if (v < in.list[K - 1]) insert_k(in.list, v);
+        }
+    }
+    // The lane's bound by the rule above; it is live until nothing more can change its answer.
+    __device__ __forceinline__ uint32_t bound(bool active, bool& live) const
+    {
+        const bool open = count < max_count;
+        live = active && (K > 0 || open);
+        if (open) return rb;
+        if constexpr (K > 0) return bound_bits(in.list[K - 1]);
+        return 0u;
+    }
+    __device__ __forceinline__ void store(long long j) const
+    {
+        count_out[j] = (int32_t)min(count, max_count);
+        if constexpr (K > 0) in.store(j);
+    }
+    __device__ __forceinline__ void store_none(long long j) const
+    {
+        count_out[j] = 0;
+        in.store_none(j);
+    }
+};
 
 // P == 0: one thread per query.
 __global__ __launch_bounds__(kBlock) void nearest_within_none_kernel(long long Q, int k, int32_t* __restrict__ count_out,
@@ -47,8 +82,25 @@ __global__ __launch_bounds__(kBlock) void nearest_within_none_kernel(long long Q
                                                                      float* __restrict__ dist2_out)
 {
     const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (j < Q) store_none_within(j, k, count_out, idx_out, dist2_out);
+    if (j < Q) LaneWithin<0>{{k, nullptr, idx_out, dist2_out}, nullptr, 0u, count_out}.store_none(j);
 }
+
+// amdgpu_waves_per_eu(8): at K = 16 the compiler otherwise settles one register above the 64 that 8 waves allow.
+template <int K>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) void nearest_within_wave_kernel(
+    IndexView ix, const float* __restrict__ queries, long long Q, const uint64_t* __restrict__ qkeys,
+    const uint32_t* __restrict__ qorder, const float* __restrict__ r2, int k, uint32_t max_count,
+    const int32_t* __restrict__ exclude, int32_t* __restrict__ count_out, int32_t* __restrict__ idx_out,
+    float* __restrict__ dist2_out, uint32_t* __restrict__ hard, Counters* __restrict__ counters)
+{
+    LaneWithin<K> sr{{k, exclude, idx_out, dist2_out}, r2, max_count, count_out};
+    lane_walk(sr, ix, queries, Q, qkeys, qorder, hard, counters);
+}
+
+// K = 16 alone keeps the walk in a body of its own, lane_walk's text with the searcher written out.  It sits at
+// exactly the 64 registers of 8 waves per SIMD, and through lane_walk the same instructions come out with other
+// register numbers and run 5-9% slower where the lane path dominates (profiles/nearest_walk_refactor.md).  A
+// change to lane_walk is made here as well.  The two functions below are LaneWithin's eval and bound for it.
 
 // The lane's count and list against the point held by lane c of `pt`, broadcast to every lane.
 template <int K>
@@ -77,9 +129,8 @@ __device__ __forceinline__ uint32_t bound_within(bool active, uint32_t count, ui
     return 0u;
 }
 
-// amdgpu_waves_per_eu(8): at K = 16 the compiler otherwise settles one register above the 64 that 8 waves allow.
 template <int K>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) void nearest_within_wave_kernel(
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) void nearest_within_wave_own_kernel(
     IndexView ix, const float* __restrict__ queries, long long Q, const uint64_t* __restrict__ qkeys,
     const uint32_t* __restrict__ qorder, const float* __restrict__ r2, int k, uint32_t max_count,
     const int32_t* __restrict__ exclude, int32_t* __restrict__ count_out, int32_t* __restrict__ idx_out,
@@ -107,7 +158,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
         reach = radius_bits(r2[j], rb);
     }
     const bool active = inq && reach && finite3(q.x, q.y, q.z);
-    if (inq && !active) store_none_within(j, k, count_out, idx_out, dist2_out);
+    if (inq && !active) LaneWithin<0>{{k, nullptr, idx_out, dist2_out}, nullptr, 0u, count_out}.store_none(j);
     if (!__ballot(active)) return;
 
     const long long P = ix.P, nleaves = ix.nleaves;
@@ -202,34 +253,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
     }
 }
 
-// k above kLaneKMax: a query that is not finite or whose radius takes nothing is answered here, every other
-// one goes to the hard list.
-__global__ __launch_bounds__(kBlock) void nearest_within_route_kernel(const float* __restrict__ queries, long long Q,
-                                                                      const uint32_t* __restrict__ qorder,
-                                                                      const float* __restrict__ r2, int k,
-                                                                      int32_t* __restrict__ count_out, int32_t* __restrict__ idx_out,
-                                                                      float* __restrict__ dist2_out, uint32_t* __restrict__ hard,
-                                                                      Counters* __restrict__ counters)
-{
-    const long long s = (long long)blockIdx.x * kBlock + threadIdx.x;
-    long long j = 0;
-    bool inq = s < Q;
-    if (inq) {
-        j = qorder[s];
-        inq = j < Q;
-    }
-    bool active = false;
-    if (inq) {
-        uint32_t rb;
-        active = radius_bits(r2[j], rb) && finite3(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2]);
-        if (!active) store_none_within(j, k, count_out, idx_out, dist2_out);
-    }
-    push_hard(active, s, lane_id(), hard, counters);
-}
-
-// One wave per hard query.  Lane i holds the i-th best in range (~0: none yet); kth is lane k - 1's value, read
-// again after every insertion; count is wave-uniform.  LIST is k > 0: without it there is no list, kth is 0
-// (nothing is below it) and a saturated query leaves every loop.
+// Two instantiations: with k as a run-time condition of the loops the kernel needs 104-106 SGPRs, 7 waves per SIMD.
 template <bool LIST>
 __global__ __launch_bounds__(kBlock) void nearest_within_hard_kernel(IndexView ix, const float* __restrict__ queries, long long Q,
                                                                      const uint64_t* __restrict__ qkeys,
@@ -240,71 +264,8 @@ __global__ __launch_bounds__(kBlock) void nearest_within_hard_kernel(IndexView i
                                                                      float* __restrict__ dist2_out, const uint32_t* __restrict__ hard,
                                                                      const Counters* __restrict__ counters)
 {
-    const int lane = lane_id();
-    const long long P = ix.P, nleaves = ix.nleaves;
-    const uint32_t nhard = min(counters->hard, (uint32_t)Q);
-    const uint32_t nw = gridDim.x * kWaves;
-    for (uint32_t h = blockIdx.x * kWaves + threadIdx.x / kWave; h < nhard; h += nw) {
-        const long long s = hard[h];
-        if (s >= Q) continue;  // written by the launch before: below Q by construction
-        const long long j = qorder[s];
-        if (j >= Q) continue;
-        const float4 q = make_float4(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], 0.f);
-        const uint32_t excl = excluded_row(exclude, j);
-        uint32_t rb;
-        if (!radius_bits(r2[j], rb)) continue;  // never listed: answered by the launch before
-        const long long L = find_leaf(ix.leaf_keys, nleaves, qkeys[s], lane);
-        uint64_t top = ~0ull, kth = LIST ? ~0ull : 0ull;
-        uint32_t count = 0;
-        uint32_t bnd = rb;  // the bound by the rule above, formed again after every leaf
-
-        // The 64 points of leaf C, one per lane: those in range are counted, and those of them below the k-th
-        // best are inserted one by one, lowest lane first, as in nearest_k_hard_kernel.
-        auto batch = [&](long long C) {
-            const long long c = C * kLeaf + lane;
-            uint64_t v = ~0ull;
-            if (c < P) v = pack_unless(q, ix.sp[c], excl);
-            const bool in = in_reach(v, rb);
-            count += (uint32_t)__popcll(__ballot(in));
-            uint64_t m = LIST ? __ballot(in && v < kth) : 0ull;
-            while (m) {
-                const int b = __builtin_ctzll(m);
-                m &= m - 1;
-                const uint64_t cv = readlane_u64(v, b);
-                if (!(cv < kth)) continue;  // wave-uniform: the bound has come down since the ballot
-                const int rank = __popcll(__ballot(top < cv));  // the entries ascend: lanes 0 .. rank - 1; rank < k
-                const uint64_t up = wave_shr1_u64(top);
-                top = lane > rank ? up : (lane == rank ? cv : top);
-                kth = readlane_u64(top, k - 1);
-            }
-            bnd = count < max_count ? rb : bound_bits(kth);
-        };
-
-        for (long long C = max(L - 1, 0ll); C <= min(L + 1, nleaves - 1); C++) batch(C);
-        // with k == 0 a saturated query is finished: a wave-uniform way out of every loop
-        for (int s0 = 0; s0 < ix.nsuper && (LIST || count < max_count); s0 += kWave) {  // one super-box per lane
-            const int sidx = s0 + lane;
-            bool pass = false;
-            if (sidx < ix.nsuper) pass = box_point_lb(ix.supers[sidx], q) <= bnd;
-            uint64_t smask = __ballot(pass);
-            while (smask && (LIST || count < max_count)) {
-                const int S = s0 + __builtin_ctzll(smask);
-                smask &= smask - 1;
-                const long long l = (long long)S * kFan + lane;
-                uint32_t llb = 0xffffffffu;  // above every bound: no leaf, or one of the seed
-                if (l < nleaves && (l < L - 1 || l > L + 1)) llb = box_point_lb(ix.leaves[l], q);
-                uint64_t lmask = __ballot(llb <= bnd);
-                while (lmask && (LIST || count < max_count)) {
-                    const int b = __builtin_ctzll(lmask);
-                    lmask &= lmask - 1;
-                    if ((uint32_t)__builtin_amdgcn_readlane((int)llb, b) > bnd) continue;
-                    batch((long long)S * kFan + b);
-                }
-            }
-        }
-        if (lane == 0) count_out[j] = (int32_t)min(count, max_count);
-        if (LIST && lane < k) store_result(top, j * k + lane, idx_out, dist2_out);
-    }
+    hard_list_walk<true, LIST>(ix, queries, Q, qkeys, qorder, r2, k, max_count, exclude, count_out, idx_out, dist2_out, hard,
+                               counters);
 }
 
 // The query scratch is nearest_query's: the counter word, the (key, row) sort, the hard list.
@@ -314,95 +275,60 @@ size_t query_within_scratch_bytes(long long P, long long Q, int k)
 }
 
 template <int K>
-void launch_within_wave(hipStream_t s, unsigned nwg, const IndexView& ix, const float* queries, long long Q, const QueryLayout& l,
-                        const float* r2, int k, int max_count, const int32_t* exclude, int32_t* count_out, int32_t* idx_out,
-                        float* dist2_out)
+constexpr auto within_wave_kernel()
 {
-    HIDEGS_LAUNCH("nearest_within_wave", nearest_within_wave_kernel<K>, dim3(nwg), dim3(kBlock), 0, s, ix, queries, Q,
-                  l.sort.keys_sorted, l.sort.vals_sorted, r2, k, (uint32_t)max_count, exclude, count_out, idx_out, dist2_out,
-                  l.hard, l.counters);
+    if constexpr (K == kLaneKMax)
+        return &nearest_within_wave_own_kernel<K>;
+    else
+        return &nearest_within_wave_kernel<K>;
+}
+
+template <int K>
+void launch_within_wave(const QueryCall& c, const float* queries, long long Q, const float* r2, int k, int max_count,
+                        const int32_t* exclude, int32_t* count_out, int32_t* idx_out, float* dist2_out)
+{
+    HIDEGS_LAUNCH("nearest_within_wave", within_wave_kernel<K>(), dim3(c.nb), dim3(kBlock), 0, c.s, c.ix, queries, Q,
+                  c.l.sort.keys_sorted, c.l.sort.vals_sorted, r2, k, (uint32_t)max_count, exclude, count_out, idx_out, dist2_out,
+                  c.l.hard, c.l.counters);
 }
 
 int query_within(const void* index, size_t index_bytes, long long P, void* scratch, size_t scratch_bytes, const float* queries,
                  long long Q, const float* r2, int k, int max_count, const int32_t* exclude, int32_t* count_out,
                  int32_t* idx_out, float* dist2_out, void* stream)
 {
-    hipStream_t s = as_stream(stream);
-    if (int rc = take_async_error("hidegs_nearest_query_within", s)) return rc;
-    if (k < 0 || k > kNearestKMax) return fail(HIDEGS_E_ARG, "nearest_query_within: k must be in [0, 64]");
-    if (max_count < std::max(k, 1))
-        return fail(HIDEGS_E_ARG, "nearest_query_within: max_count must be in [max(k, 1), 2^31)");
-    if (!in_range(P)) return fail(HIDEGS_E_ARG, "nearest_query_within: P must be in [0, 2^31)");
-    if (!in_range(Q)) return fail(HIDEGS_E_ARG, "nearest_query_within: Q must be in [0, 2^31)");
-    if (Q == 0) return 0;
-    if (!queries) return fail(HIDEGS_E_ARG, "nearest_query_within: NULL queries");
-    if (!r2) return fail(HIDEGS_E_ARG, "nearest_query_within: NULL r2");
-    if (!count_out) return fail(HIDEGS_E_ARG, "nearest_query_within: NULL count_out");
-    if (k > 0 && !idx_out) return fail(HIDEGS_E_ARG, "nearest_query_within: NULL idx_out with k > 0");
-    if (k > 0 && !dist2_out) return fail(HIDEGS_E_ARG, "nearest_query_within: NULL dist2_out with k > 0");
-    if (P > 0) {
-        if (!index || !aligned16(index) || index_bytes < index_layout(nullptr, P).total)
-            return fail(HIDEGS_E_ARG, "nearest_query_within: index buffer NULL, not 16-byte aligned or too small for P");
-        if (!scratch || !aligned16(scratch) || scratch_bytes < query_layout(nullptr, Q).total)
-            return fail(HIDEGS_E_ARG, "nearest_query_within: scratch buffer NULL, not 16-byte aligned or too small");
-    } else {
-        index = nullptr, index_bytes = 0, scratch = nullptr, scratch_bytes = 0;  // not used
-    }
-    struct Span {
-        const void* p;
-        size_t n;
-        const char* name;
-    };
     const size_t out_bytes = (size_t)Q * (size_t)k * 4;  // 0 at k == 0: those two overlap nothing
-    const Span outputs[] = {{count_out, (size_t)Q * 4, "count_out"}, {idx_out, out_bytes, "idx_out"}, {dist2_out, out_bytes, "dist2_out"}};
-    const Span inputs[] = {{queries, (size_t)Q * 12, "queries"},
-                           {r2, (size_t)Q * 4, "r2"},
-                           {exclude, (size_t)Q * 4, "exclude"},
-                           {index, index_bytes, "the index"},
-                           {scratch, scratch_bytes, "scratch"}};
-    for (const auto& in : inputs)
-        for (const auto& out : outputs)
-            if (overlap(out.p, out.n, in.p, in.n))
-                return fail(HIDEGS_E_ARG, std::string("nearest_query_within: ") + out.name + " overlaps " + in.name);
-    for (int a = 0; a < 3; a++)
-        for (int b = a + 1; b < 3; b++)
-            if (overlap(outputs[a].p, outputs[a].n, outputs[b].p, outputs[b].n))
-                return fail(HIDEGS_E_ARG, std::string("nearest_query_within: ") + outputs[b].name + " overlaps " + outputs[a].name);
-    const unsigned nb = (unsigned)ceil_div(Q, kBlock);  // a thread per query; in the wave kernel, a wave per 64 sorted queries
-    if (P == 0) {
-        HIDEGS_LAUNCH("nearest_within_none", nearest_within_none_kernel, dim3(nb), dim3(kBlock), 0, s, Q, k, count_out, idx_out,
-                      dist2_out);
-        return check_launch("nearest_query_within", s, 0);
-    }
-    const IndexLayout il = index_layout(const_cast<void*>(index), P);
-    const IndexView ix{il.frame, il.sp, il.leaves, il.supers, il.leaf_keys, P, il.nleaves, il.nsuper};
-    const QueryLayout l = query_layout(scratch, Q);
-    if (hipMemsetAsync(l.counters, 0, sizeof(Counters), s) != hipSuccess)
-        return fail(HIDEGS_E_HIP, "nearest_query_within: clearing the counter failed");
-    HIDEGS_LAUNCH("nearest_query_keys", nearest_query_keys_kernel, dim3(nb), dim3(kBlock), 0, s, queries, Q, ix.frame,
-                  l.sort.keys, l.sort.vals);
-    if (int rc = sort_pairs_u64(l.sort.sort_tmp, l.sort.sort_bytes, l.sort.keys, l.sort.keys_sorted, l.sort.vals,
-                                l.sort.vals_sorted, Q, 0, 3 * kMortonBits, s))
-        return rc;
+    const char* with_k = k > 0 ? " with k > 0" : nullptr;
+    QueryCall c;
+    if (!begin_query(c, "nearest_query_within", stream, index, index_bytes, P, scratch, scratch_bytes, queries, Q, k, 0,
+                     kNearestKMax, max_count < std::max(k, 1) ? "max_count must be in [max(k, 1), 2^31)" : nullptr,
+                     {{r2, (size_t)Q * 4, "r2", ""}, {exclude, (size_t)Q * 4, "exclude"}},
+                     {{count_out, (size_t)Q * 4, "count_out", ""},
+                      {idx_out, out_bytes, "idx_out", with_k},
+                      {dist2_out, out_bytes, "dist2_out", with_k}},
+                     [&](const QueryCall& c) {
+                         HIDEGS_LAUNCH("nearest_within_none", nearest_within_none_kernel, dim3(c.nb), dim3(kBlock), 0, c.s, Q, k,
+                                       count_out, idx_out, dist2_out);
+                     }))
+        return c.rc;
     if (k == 0)
-        launch_within_wave<0>(s, nb, ix, queries, Q, l, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
+        launch_within_wave<0>(c, queries, Q, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
     else if (k <= 4)
-        launch_within_wave<4>(s, nb, ix, queries, Q, l, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
+        launch_within_wave<4>(c, queries, Q, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
     else if (k <= 8)
-        launch_within_wave<8>(s, nb, ix, queries, Q, l, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
+        launch_within_wave<8>(c, queries, Q, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
     else if (k <= kLaneKMax)
-        launch_within_wave<kLaneKMax>(s, nb, ix, queries, Q, l, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
+        launch_within_wave<kLaneKMax>(c, queries, Q, r2, k, max_count, exclude, count_out, idx_out, dist2_out);
     else
-        HIDEGS_LAUNCH("nearest_within_route", nearest_within_route_kernel, dim3(nb), dim3(kBlock), 0, s, queries, Q,
-                      l.sort.vals_sorted, r2, k, count_out, idx_out, dist2_out, l.hard, l.counters);
-    const dim3 hgrid(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves)));
+        HIDEGS_LAUNCH("nearest_within_route", nearest_route_kernel<LaneWithin<0>>, dim3(c.nb), dim3(kBlock), 0, c.s, queries, Q,
+                      c.l.sort.vals_sorted, LaneWithin<0>{{k, exclude, idx_out, dist2_out}, r2, (uint32_t)max_count, count_out},
+                      c.l.hard, c.l.counters);
     if (k == 0)
-        HIDEGS_LAUNCH("nearest_within_hard", nearest_within_hard_kernel<false>, hgrid, dim3(kBlock), 0, s, ix, queries, Q,
-                      l.sort.keys_sorted, l.sort.vals_sorted, r2, k, (uint32_t)max_count, exclude, count_out, idx_out,
-                      dist2_out, l.hard, l.counters);
+        HIDEGS_LAUNCH("nearest_within_hard", nearest_within_hard_kernel<false>, hard_grid(Q), dim3(kBlock), 0, c.s, c.ix, queries, Q,
+                      c.l.sort.keys_sorted, c.l.sort.vals_sorted, r2, k, (uint32_t)max_count, exclude, count_out, idx_out,
+                      dist2_out, c.l.hard, c.l.counters);
     else
-        HIDEGS_LAUNCH("nearest_within_hard", nearest_within_hard_kernel<true>, hgrid, dim3(kBlock), 0, s, ix, queries, Q,
-                      l.sort.keys_sorted, l.sort.vals_sorted, r2, k, (uint32_t)max_count, exclude, count_out, idx_out,
-                      dist2_out, l.hard, l.counters);
-    return check_launch("nearest_query_within", s, 0);
+        HIDEGS_LAUNCH("nearest_within_hard", nearest_within_hard_kernel<true>, hard_grid(Q), dim3(kBlock), 0, c.s, c.ix, queries, Q,
+                      c.l.sort.keys_sorted, c.l.sort.vals_sorted, r2, k, (uint32_t)max_count, exclude, count_out, idx_out,
+                      dist2_out, c.l.hard, c.l.counters);
+    return check_launch("nearest_query_within", c.s, 0);
 }

@@ -54,6 +54,52 @@ def _size_class(q: int) -> int:
     return min(max(1024, 1 << (q - 1).bit_length()), _MAX)
 
 
+def _need_k(k, least: int) -> int:
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise RuntimeError(f"nearest: k must be an integer, got {type(k).__name__}")
+    k = int(k)
+    if not least <= k <= K_MAX:
+        raise RuntimeError(f"nearest: k must be in [{least}, {K_MAX}], got {k}")
+    return k
+
+
+def _need_exclude(exclude, Q: int) -> dict:
+    """`exclude` is None or a contiguous (Q,) int32 tensor; returns it by name for the device check."""
+    if exclude is None:
+        return {}
+    if not isinstance(exclude, torch.Tensor):
+        raise RuntimeError("nearest: exclude is not a tensor")
+    if exclude.dtype != torch.int32 or exclude.dim() != 1 or not exclude.is_contiguous():
+        raise RuntimeError(f"nearest: exclude: expected a contiguous 1-D int32 tensor, got {exclude.dtype} of "
+                           f"shape {tuple(exclude.shape)}")
+    if exclude.numel() != Q:
+        raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
+    return {"exclude": exclude}
+
+
+def _need_out(out, want, Q: int) -> dict:
+    """`out` is None or one tensor per entry of `want`, the expected (name, dtype, shape); a shape of None accepts
+    any contiguous 1-D tensor of Q entries.  Returns them by name for the device check."""
+    if out is None:
+        return {}
+    if not isinstance(out, (tuple, list)) or len(out) != len(want):
+        raise RuntimeError(f"nearest: out must be a {'pair' if len(want) == 2 else 'triple'} "
+                           f"({', '.join(what[len('out '):] for what, _, _ in want)})")
+    for t, (what, dtype, shape) in zip(out, want):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"nearest: {what} is not a tensor")
+        if shape is None:
+            if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+                raise RuntimeError(f"nearest: {what}: expected a contiguous 1-D {dtype} tensor, got {t.dtype} of "
+                                   f"shape {tuple(t.shape)}")
+            if t.numel() != Q:
+                raise RuntimeError(f"nearest: {what} has {t.numel()} entries, queries has {Q} rows")
+        elif t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"nearest: {what}: expected a contiguous {shape} {dtype} tensor, got "
+                               f"{t.dtype} of shape {tuple(t.shape)}")
+    return {what: t for t, (what, _, _) in zip(out, want)}
+
+
 class NearestIndex:
     """An index over `points`, a contiguous (P, 3) float32 GPU tensor, built on the current stream.
 
@@ -80,6 +126,23 @@ class NearestIndex:
                                         points.data_ptr(), self.P, _lib.stream_handle(self.device))
             _lib.check(rc, "nearest_build")
 
+    def _need_device(self, Q: int, **tensors) -> None:
+        if Q:
+            _lib.device_of(*tensors.values())
+        _need_gpu(self.device, **tensors)
+
+    def _scratch_for(self, stream, Q: int, need_bytes):
+        """The scratch tensor of `stream` and Q's size class, of need_bytes(that class's Q) bytes at least; None for
+        an empty cloud, which needs none.  One tensor serves all three queries: their layout is the same."""
+        if not self.P:
+            return None
+        key = (stream, _size_class(Q))
+        need = need_bytes(key[1])
+        tmp = self._scratch.get(key)
+        if tmp is None or tmp.numel() < need:
+            tmp = self._scratch[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return tmp
+
     def query(self, queries: torch.Tensor, out: Tuple[torch.Tensor, torch.Tensor] = None
               ) -> Tuple[torch.Tensor, torch.Tensor]:
         """(idx, d2) of `queries`, a contiguous (Q, 3) float32 tensor on the index's device: idx (Q,) int32, the
@@ -87,20 +150,8 @@ class NearestIndex:
         infinite coordinate or the cloud has no finite row), and d2 (Q,) float32, its squared distance (+inf
         with -1).  out=(idx, d2) reuses two such tensors.  Runs on the current stream; no host synchronisation."""
         Q = _need_rows(queries, "queries")
-        if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise RuntimeError("nearest: out must be a pair (idx, d2)")
-            for what, t, dtype in (("out idx", out[0], torch.int32), ("out d2", out[1], torch.float32)):
-                if not isinstance(t, torch.Tensor):
-                    raise RuntimeError(f"nearest: {what} is not a tensor")
-                if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
-                    raise RuntimeError(f"nearest: {what}: expected a contiguous 1-D {dtype} tensor, got {t.dtype} of "
-                                       f"shape {tuple(t.shape)}")
-                if t.numel() != Q:
-                    raise RuntimeError(f"nearest: {what} has {t.numel()} entries, queries has {Q} rows")
-        if Q:
-            _lib.device_of(queries, *(out or ()))
-        _need_gpu(self.device, queries=queries, **({} if out is None else {"out idx": out[0], "out d2": out[1]}))
+        outs = _need_out(out, (("out idx", torch.int32, None), ("out d2", torch.float32, None)), Q)
+        self._need_device(Q, queries=queries, **outs)
         with torch.cuda.device(self.device):
             idx, d2 = out if out is not None else (torch.empty(Q, dtype=torch.int32, device=self.device),
                                                    torch.empty(Q, dtype=torch.float32, device=self.device))
@@ -108,13 +159,7 @@ class NearestIndex:
                 return idx, d2
             L = _lib.lib()
             stream = _lib.stream_handle(self.device)
-            tmp = None
-            if self.P:
-                key = (stream, _size_class(Q))
-                tmp = self._scratch.get(key)
-                if tmp is None:
-                    tmp = self._scratch[key] = torch.empty(L.hidegs_nearest_query_scratch_bytes(self.P, key[1]),
-                                                           dtype=torch.uint8, device=self.device)
+            tmp = self._scratch_for(stream, Q, lambda q: L.hidegs_nearest_query_scratch_bytes(self.P, q))
             rc = L.hidegs_nearest_query(_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp),
                                         0 if tmp is None else tmp.numel(), queries.data_ptr(), Q, idx.data_ptr(),
                                         d2.data_ptr(), stream)
@@ -130,36 +175,10 @@ class NearestIndex:
         of candidates, and every slot of a query with a NaN or infinite coordinate, hold -1 and +inf.
         out=(idx, d2) reuses two such tensors.  Runs on the current stream; no host synchronisation."""
         Q = _need_rows(queries, "queries")
-        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
-            raise RuntimeError(f"nearest: k must be an integer, got {type(k).__name__}")
-        k = int(k)
-        if not 1 <= k <= K_MAX:
-            raise RuntimeError(f"nearest: k must be in [1, {K_MAX}], got {k}")
-        if exclude is not None:
-            if not isinstance(exclude, torch.Tensor):
-                raise RuntimeError("nearest: exclude is not a tensor")
-            if exclude.dtype != torch.int32 or exclude.dim() != 1 or not exclude.is_contiguous():
-                raise RuntimeError(f"nearest: exclude: expected a contiguous 1-D int32 tensor, got {exclude.dtype} of "
-                                   f"shape {tuple(exclude.shape)}")
-            if exclude.numel() != Q:
-                raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
-        if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise RuntimeError("nearest: out must be a pair (idx, d2)")
-            for what, t, dtype in (("out idx", out[0], torch.int32), ("out d2", out[1], torch.float32)):
-                if not isinstance(t, torch.Tensor):
-                    raise RuntimeError(f"nearest: {what} is not a tensor")
-                if t.dtype != dtype or tuple(t.shape) != (Q, k) or not t.is_contiguous():
-                    raise RuntimeError(f"nearest: {what}: expected a contiguous ({Q}, {k}) {dtype} tensor, got "
-                                       f"{t.dtype} of shape {tuple(t.shape)}")
-        tensors = {"queries": queries}
-        if exclude is not None:
-            tensors["exclude"] = exclude
-        if out is not None:
-            tensors.update({"out idx": out[0], "out d2": out[1]})
-        if Q:
-            _lib.device_of(*tensors.values())
-        _need_gpu(self.device, **tensors)
+        k = _need_k(k, 1)
+        tensors = {"queries": queries, **_need_exclude(exclude, Q),
+                   **_need_out(out, (("out idx", torch.int32, (Q, k)), ("out d2", torch.float32, (Q, k))), Q)}
+        self._need_device(Q, **tensors)
         with torch.cuda.device(self.device):
             idx, d2 = out if out is not None else (torch.empty((Q, k), dtype=torch.int32, device=self.device),
                                                    torch.empty((Q, k), dtype=torch.float32, device=self.device))
@@ -167,14 +186,7 @@ class NearestIndex:
                 return idx, d2
             L = _lib.lib()
             stream = _lib.stream_handle(self.device)
-            tmp = None
-            if self.P:
-                # query's scratch tensors serve: the layout is the same, whatever k is
-                key = (stream, _size_class(Q))
-                need = L.hidegs_nearest_query_k_scratch_bytes(self.P, key[1], k)
-                tmp = self._scratch.get(key)
-                if tmp is None or tmp.numel() < need:
-                    tmp = self._scratch[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            tmp = self._scratch_for(stream, Q, lambda q: L.hidegs_nearest_query_k_scratch_bytes(self.P, q, k))
             rc = L.hidegs_nearest_query_k(_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp),
                                           0 if tmp is None else tmp.numel(), queries.data_ptr(), Q, k,
                                           _lib.ptr(exclude), idx.data_ptr(), d2.data_ptr(), stream)
@@ -194,11 +206,7 @@ class NearestIndex:
         +inf.  exclude: as for query_k; the excluded row is neither counted nor listed.  out=(count, idx, d2)
         reuses three such tensors.  Runs on the current stream; no host synchronisation."""
         Q = _need_rows(queries, "queries")
-        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
-            raise RuntimeError(f"nearest: k must be an integer, got {type(k).__name__}")
-        k = int(k)
-        if not 0 <= k <= K_MAX:
-            raise RuntimeError(f"nearest: k must be in [0, {K_MAX}], got {k}")
+        k = _need_k(k, 0)
         if max_count is None:
             max_count = _MAX
         if isinstance(max_count, bool) or not isinstance(max_count, numbers.Integral):
@@ -214,34 +222,10 @@ class NearestIndex:
                 raise RuntimeError(f"nearest: r2 has {r2.numel()} entries, queries has {Q} rows")
         elif isinstance(r2, bool) or not isinstance(r2, numbers.Real):
             raise RuntimeError(f"nearest: r2 must be a number or a tensor, got {type(r2).__name__}")
-        if exclude is not None:
-            if not isinstance(exclude, torch.Tensor):
-                raise RuntimeError("nearest: exclude is not a tensor")
-            if exclude.dtype != torch.int32 or exclude.dim() != 1 or not exclude.is_contiguous():
-                raise RuntimeError(f"nearest: exclude: expected a contiguous 1-D int32 tensor, got {exclude.dtype} of "
-                                   f"shape {tuple(exclude.shape)}")
-            if exclude.numel() != Q:
-                raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
-        if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 3:
-                raise RuntimeError("nearest: out must be a triple (count, idx, d2)")
-            for what, t, dtype, shape in (("out count", out[0], torch.int32, (Q,)), ("out idx", out[1], torch.int32, (Q, k)),
-                                          ("out d2", out[2], torch.float32, (Q, k))):
-                if not isinstance(t, torch.Tensor):
-                    raise RuntimeError(f"nearest: {what} is not a tensor")
-                if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise RuntimeError(f"nearest: {what}: expected a contiguous {shape} {dtype} tensor, got "
-                                       f"{t.dtype} of shape {tuple(t.shape)}")
-        tensors = {"queries": queries}
-        if isinstance(r2, torch.Tensor):
-            tensors["r2"] = r2
-        if exclude is not None:
-            tensors["exclude"] = exclude
-        if out is not None:
-            tensors.update({"out count": out[0], "out idx": out[1], "out d2": out[2]})
-        if Q:
-            _lib.device_of(*tensors.values())
-        _need_gpu(self.device, **tensors)
+        tensors = {"queries": queries, **({"r2": r2} if isinstance(r2, torch.Tensor) else {}), **_need_exclude(exclude, Q),
+                   **_need_out(out, (("out count", torch.int32, (Q,)), ("out idx", torch.int32, (Q, k)),
+                                     ("out d2", torch.float32, (Q, k))), Q)}
+        self._need_device(Q, **tensors)
         with torch.cuda.device(self.device):
             count, idx, d2 = out if out is not None else (torch.empty(Q, dtype=torch.int32, device=self.device),
                                                           torch.empty((Q, k), dtype=torch.int32, device=self.device),
@@ -252,14 +236,7 @@ class NearestIndex:
                 r2 = torch.full((Q,), float(r2), dtype=torch.float32, device=self.device)  # a fill kernel: no synchronisation
             L = _lib.lib()
             stream = _lib.stream_handle(self.device)
-            tmp = None
-            if self.P:
-                # query's scratch tensors serve: the layout is the same
-                key = (stream, _size_class(Q))
-                need = L.hidegs_nearest_query_within_scratch_bytes(self.P, key[1], k)
-                tmp = self._scratch.get(key)
-                if tmp is None or tmp.numel() < need:
-                    tmp = self._scratch[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            tmp = self._scratch_for(stream, Q, lambda q: L.hidegs_nearest_query_within_scratch_bytes(self.P, q, k))
             rc = L.hidegs_nearest_query_within(_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp),
                                                0 if tmp is None else tmp.numel(), queries.data_ptr(), Q, r2.data_ptr(), k,
                                                max_count, _lib.ptr(exclude), count.data_ptr(),

@@ -45,11 +45,14 @@ def test_restated_constants_match_nearest_hip():
              for name, text in (("kLeaf", src), ("kFan", src), ("kBailout", src), ("kSpanBail", src),
                                 ("kWave", common))}
     assert found == {"kLeaf": K_LEAF, "kFan": K_FAN, "kBailout": K_BAILOUT, "kSpanBail": K_SPAN_BAIL, "kWave": K_WAVE}
-    assert src.count("s0 += kWave)") == 2  # phase 1's walk and phase 2's
+    assert src.count("s0 += kWave)") == 2  # phase 1's walk (lane_walk, of all three queries) and phase 2's
+    assert src.count("> kBailout)") == 1 and src.count("> kSpanBail)") == 1  # that walk's two ways to phase 2
     found = {name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1)) for name in ("kHardGrid", "kBlock")}
     assert found["kHardGrid"] == K_HARD_GRID and HARD_WAVES == K_HARD_GRID * (found["kBlock"] // K_WAVE)
     assert "constexpr int kWaves = kBlock / kWave;" in src
-    assert len(re.findall(r"nearest_hard_kernel, dim3\(std::min<unsigned>\(kHardGrid, \(unsigned\)ceil_div\(Q, kWaves\)\)\)", src)) == 1
+    # the grid of every wave-per-query launch, of all three queries
+    assert src.count("dim3 hard_grid(long long Q) { return dim3(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves))); }") == 1
+    assert len(re.findall(r"nearest_hard_kernel, hard_grid\(Q\),", src)) == 1
     assert src.count("h < nhard; h += nw)") == 1 and "nw = gridDim.x * kWaves;" in src
 
 

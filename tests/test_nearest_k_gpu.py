@@ -41,9 +41,11 @@ def test_restated_constants_match_nearest_k_h():
     launched = re.findall(r"launch_k_wave<(\w+)>\(", src)
     assert tuple(LANE_K_MAX if n == "kLaneKMax" else int(n) for n in launched) == LANE_KS
     assert re.findall(r"k <= (\w+)\)\n\s+launch_k_wave<(\w+)>", src) == [("4", "4"), ("8", "8"), ("kLaneKMax", "kLaneKMax")]
-    assert src.count("s0 += kWave)") == 2  # the lane walk and the wave walk
-    # the wave-per-query launch is capped as the 1-NN query's (K_HARD_GRID and HARD_WAVES of test_nearest_gpu)
-    assert len(re.findall(r"nearest_k_hard_kernel, dim3\(std::min<unsigned>\(kHardGrid, \(unsigned\)ceil_div\(Q, kWaves\)\)\)", src)) == 1
+    # the wave walk (hard_list_walk, of both list queries); the lane walk is nearest.hip's (test_nearest_gpu)
+    assert src.count("s0 += kWave)") == 1
+    assert src.count("lane_walk(sr, ix, queries, Q, qkeys, qorder, hard, counters);") == 1
+    # the wave-per-query launch is capped as the 1-NN query's (hard_grid, K_HARD_GRID and HARD_WAVES of test_nearest_gpu)
+    assert len(re.findall(r"nearest_k_hard_kernel, hard_grid\(Q\),", src)) == 1
     assert src.count("h < nhard; h += nw)") == 1 and "nw = gridDim.x * kWaves;" in src
 
 

@@ -29,15 +29,19 @@ def test_restated_constants_match_nearest_within_h():
     import re
     here = os.path.dirname(os.path.abspath(__file__))
     src = open(os.path.join(here, "..", "hidegs_amd", "csrc", "nearest_within.h")).read()
-    assert re.findall(r"launch_within_wave<(\w+)>\(s,", src) == ["0", "4", "8", "kLaneKMax"]
+    assert re.findall(r"launch_within_wave<(\w+)>\(c,", src) == ["0", "4", "8", "kLaneKMax"]
     assert re.findall(r"k (?:==|<=) (\w+)\)\n\s+launch_within_wave<(\w+)>", src) == [("0", "0"), ("4", "4"), ("8", "8"),
                                                                                       ("kLaneKMax", "kLaneKMax")]
-    assert src.count("> kBailout)") == 1 and src.count("> kSpanBail)") == 1 and src.count("s0 += kWave)") == 2
-    # the wave-per-query launch is capped as the 1-NN query's (K_HARD_GRID and HARD_WAVES of test_nearest_gpu), in
-    # both forms: without a list at k = 0, with one above
-    assert src.count("const dim3 hgrid(std::min<unsigned>(kHardGrid, (unsigned)ceil_div(Q, kWaves)));") == 1
-    assert re.findall(r"nearest_within_hard_kernel<(\w+)>, hgrid,", src) == ["false", "true"]
-    assert src.count("h < nhard; h += nw)") == 1 and "nw = gridDim.x * kWaves;" in src
+    # Both walks are shared: the lane walk with its two bail-outs is nearest.hip's lane_walk, the wave walk and its
+    # stride nearest_k.h's hard_list_walk, and test_nearest_gpu and test_nearest_k_gpu pin them there.  Here: that
+    # this query runs them, and that the one kernel with a lane walk of its own (K = 16) has the same three facts.
+    assert src.count("lane_walk(sr, ix, queries, Q, qkeys, qorder, hard, counters);") == 1
+    assert src.count("hard_list_walk<true, LIST>(") == 1
+    assert src.count("return &nearest_within_wave_own_kernel<K>;") == 1 and src.count("if constexpr (K == kLaneKMax)") == 1
+    assert src.count("> kBailout)") == 1 and src.count("> kSpanBail)") == 1 and src.count("s0 += kWave)") == 1
+    # the wave-per-query launch is capped as the 1-NN query's (hard_grid, K_HARD_GRID and HARD_WAVES of
+    # test_nearest_gpu), in both forms: without a list at k = 0, with one above
+    assert re.findall(r"nearest_within_hard_kernel<(\w+)>, hard_grid\(Q\),", src) == ["false", "true"]
 
 INT32_MAX = 2 ** 31 - 1
 INF, NAN = float("inf"), float("nan")

@@ -1,6 +1,6 @@
 """Build recipe for hidegs_amd/libhidegs.so (the C-ABI library of include/hidegs.h, hidegs_rows.h,
-hidegs_resize.h, hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h, hidegs_nearest_within.h and
-hidegs_voxel.h).
+hidegs_resize.h, hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h, hidegs_nearest_within.h,
+hidegs_nearest_lists.h and hidegs_voxel.h).
 
 Built in-tree with hipcc for gfx950 so the .so travels to the GPU box with the
 repository snapshot.  `python -m hidegs_amd.build` or `__graft_entry__.build()`.
@@ -39,6 +39,7 @@ HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, 
                                                          os.path.join(INCLUDE, "hidegs_nearest.h"),
                                                          os.path.join(INCLUDE, "hidegs_nearest_k.h"),
                                                          os.path.join(INCLUDE, "hidegs_nearest_within.h"),
+                                                         os.path.join(INCLUDE, "hidegs_nearest_lists.h"),
                                                          os.path.join(INCLUDE, "hidegs_voxel.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf, so the

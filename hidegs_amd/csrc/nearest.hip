@@ -45,6 +45,7 @@
 #include "../../include/hidegs_nearest.h"
 #include "../../include/hidegs_nearest_k.h"
 #include "../../include/hidegs_nearest_within.h"
+#include "../../include/hidegs_nearest_lists.h"
 #include "common.h"
 
 namespace hidegs {
@@ -750,6 +751,7 @@ dim3 hard_grid(long long Q) { return dim3(std::min<unsigned>(kHardGrid, (unsigne
 
 #include "nearest_k.h"
 #include "nearest_within.h"
+#include "nearest_lists.h"
 
 }  // namespace
 }  // namespace hidegs
@@ -845,4 +847,36 @@ extern "C" int hidegs_nearest_query_within(const void* index, size_t index_bytes
 {
     return hidegs::query_within(index, index_bytes, P, scratch, scratch_bytes, queries, Q, r2, k, max_count, exclude, count_out,
                                 idx_out, dist2_out, stream);
+}
+
+extern "C" int hidegs_nearest_index_order(const void* index, size_t index_bytes, long long P, int32_t* order_out, void* stream)
+{
+    return hidegs::index_order(index, index_bytes, P, order_out, stream);
+}
+
+extern "C" size_t hidegs_nearest_list_offsets_scratch_bytes(long long P, long long Q)
+{
+    return hidegs::list_offsets_scratch_bytes(P, Q);
+}
+
+extern "C" int hidegs_nearest_list_offsets(const void* index, size_t index_bytes, long long P, void* scratch,
+                                           size_t scratch_bytes, const float* queries, long long Q, const float* r2,
+                                           const int32_t* exclude, int32_t* starts_out, uint32_t* info_out, void* stream)
+{
+    return hidegs::list_offsets(index, index_bytes, P, scratch, scratch_bytes, queries, Q, r2, exclude, starts_out, info_out,
+                                stream);
+}
+
+extern "C" size_t hidegs_nearest_list_fill_scratch_bytes(long long P, long long Q)
+{
+    return hidegs::list_fill_scratch_bytes(P, Q);
+}
+
+extern "C" int hidegs_nearest_list_fill(const void* index, size_t index_bytes, long long P, void* scratch, size_t scratch_bytes,
+                                        const float* queries, long long Q, const float* r2, const int32_t* exclude,
+                                        const int32_t* starts, long long capacity, int32_t* rows_out, float* dist2_out,
+                                        void* stream)
+{
+    return hidegs::list_fill(index, index_bytes, P, scratch, scratch_bytes, queries, Q, r2, exclude, starts, capacity, rows_out,
+                             dist2_out, stream);
 }

@@ -1,7 +1,7 @@
 """Nearest-point index (include/hidegs_nearest.h, include/hidegs_nearest_k.h, include/hidegs_nearest_within.h,
-csrc/nearest.hip): built once over a point cloud on the GPU, then asked for the nearest point, the k nearest, or
-how many points lie within a radius (and the k nearest of those) of arbitrary positions -- exactly, lowest row
-index among equals.
+include/hidegs_nearest_lists.h, csrc/nearest.hip): built once over a point cloud on the GPU, then asked for the
+nearest point, the k nearest, how many points lie within a radius (and the k nearest of those), or every point
+within a radius as CSR neighbour lists, of arbitrary positions -- exactly, lowest row index among equals.
 
     index = NearestIndex(points)        # (P, 3) contiguous float32 GPU tensor; builds on the current stream
     idx, d2 = index.query(queries)      # (Q,) int32 (-1: none), (Q,) float32 squared distances
@@ -12,6 +12,10 @@ index among equals.
     count = index.count_within(queries, r2, exclude=None, max_count=None)   # r2: a number or a (Q,) tensor, squared
     count, idx, d2 = within(points, queries, r2, k=0, exclude=None, max_count=None)
     count = count_within(points, queries, r2, exclude=None, max_count=None)
+    lists = index.lists_within(queries, r2, exclude=None, capacity=None, distances=True)   # NeighborLists (CSR):
+    lists.starts, lists.rows, lists.d2, lists.info, lists.counts(), lists.query_of()       # every row in range
+    lists = lists_within(points, queries, r2, exclude=None, capacity=None, distances=True)
+    order = index.order()               # (P,) int32: the row at every position of the index; the lists' order
 
 The index holds its own copy of the points: rebuild it after the positions move or the rows are resized.
 """
@@ -75,6 +79,20 @@ def _need_exclude(exclude, Q: int) -> dict:
     if exclude.numel() != Q:
         raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
     return {"exclude": exclude}
+
+
+def _need_r2(r2, Q: int) -> dict:
+    """`r2` is a number or a contiguous (Q,) float32 tensor; returns the tensor by name for the device check."""
+    if isinstance(r2, torch.Tensor):
+        if r2.dtype != torch.float32 or r2.dim() != 1 or not r2.is_contiguous():
+            raise RuntimeError(f"nearest: r2: expected a number or a contiguous 1-D float32 tensor, got {r2.dtype} of "
+                               f"shape {tuple(r2.shape)}")
+        if r2.numel() != Q:
+            raise RuntimeError(f"nearest: r2 has {r2.numel()} entries, queries has {Q} rows")
+        return {"r2": r2}
+    if isinstance(r2, bool) or not isinstance(r2, numbers.Real):
+        raise RuntimeError(f"nearest: r2 must be a number or a tensor, got {type(r2).__name__}")
+    return {}
 
 
 def _need_out(out, want, Q: int) -> dict:
@@ -249,6 +267,113 @@ class NearestIndex:
         query, at most max_count.  `count_within(xyz, r2, exclude=arange(P), max_count=m) >= m` is radius outlier
         removal's keep mask."""
         return self.query_within(queries, r2, 0, exclude, max_count)[0]
+
+
+    def order(self) -> torch.Tensor:
+        """(P,) int32: the row stored at every position of the index, a permutation of 0 .. P-1 with the rows of
+        non-finite coordinates behind every candidate.  It depends on the points alone; lists_within orders every
+        list by it.  Runs on the current stream; no host synchronisation."""
+        with torch.cuda.device(self.device):
+            out = torch.empty(self.P, dtype=torch.int32, device=self.device)
+            if self.P:
+                rc = _lib.lib().hidegs_nearest_index_order(self.index.data_ptr(), self.index.numel(), self.P, out.data_ptr(),
+                                                           _lib.stream_handle(self.device))
+                _lib.check(rc, "nearest_index_order")
+        return out
+
+    def lists_within(self, queries: torch.Tensor, r2, exclude: torch.Tensor = None, capacity: int = None,
+                     distances: bool = True, out: Tuple[torch.Tensor, torch.Tensor] = None) -> "NeighborLists":
+        """Every row within a squared radius of every query, as CSR neighbour lists (NeighborLists): the list of query
+        j is rows[starts[j]:starts[j + 1]] with squared distances d2[...], exact and of any length, in ascending
+        position of the index (order()) -- a function of the points, the query, its r2 and its exclude alone.
+        r2, exclude and "in range" are query_within's.  distances=False leaves d2 None.
+
+        capacity=None sizes rows and d2 exactly: one host read of `info` (4 words) between the count and the fill,
+        the only synchronisation; it raises RuntimeError where the lists hold more than 2^31 - 1 entries.
+        capacity=int allocates that many entries, or takes out=(rows, d2) of that length (d2 None without
+        distances): no host synchronisation, capturable in a graph.  Entries at positions from `capacity` on are
+        not written, and the caller compares info with the capacity: `lists.info[0]` (and info[1], the high word)
+        is the number of entries all lists hold.  Runs on the current stream."""
+        Q = _need_rows(queries, "queries")
+        if capacity is not None:
+            if isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral):
+                raise RuntimeError(f"nearest: capacity must be an integer or None, got {type(capacity).__name__}")
+            capacity = int(capacity)
+            if not 0 <= capacity <= _MAX:
+                raise RuntimeError(f"nearest: capacity must be in [0, 2^31 - 1], got {capacity}")
+        if not isinstance(distances, bool):
+            raise RuntimeError(f"nearest: distances must be a bool, got {type(distances).__name__}")
+        r2t = _need_r2(r2, Q)
+        outs = {}
+        if out is not None:
+            if capacity is None:
+                raise RuntimeError("nearest: out=(rows, d2) needs a capacity")
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise RuntimeError("nearest: out must be a pair (rows, d2)")
+            for t, what, dtype in ((out[0], "out rows", torch.int32), (out[1], "out d2", torch.float32)):
+                if t is None and what == "out d2" and not distances:
+                    continue
+                if not isinstance(t, torch.Tensor):
+                    raise RuntimeError(f"nearest: {what} is not a tensor")
+                if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+                    raise RuntimeError(f"nearest: {what}: expected a contiguous 1-D {dtype} tensor, got {t.dtype} of "
+                                       f"shape {tuple(t.shape)}")
+                if t.numel() != capacity:
+                    raise RuntimeError(f"nearest: {what} has {t.numel()} entries, capacity is {capacity}")
+                outs[what] = t
+            if not distances and out[1] is not None:
+                raise RuntimeError("nearest: out d2 must be None without distances")
+        tensors = {"queries": queries, **r2t, **_need_exclude(exclude, Q), **outs}
+        self._need_device(Q, **tensors)
+        with torch.cuda.device(self.device):
+            L = _lib.lib()
+            stream = _lib.stream_handle(self.device)
+            starts = torch.empty(Q + 1, dtype=torch.int32, device=self.device)
+            info = torch.empty(4, dtype=torch.int32, device=self.device)
+            if Q and not r2t:
+                r2 = torch.full((Q,), float(r2), dtype=torch.float32, device=self.device)  # a fill kernel: no synchronisation
+            tmp = self._scratch_for(stream, Q, lambda q: L.hidegs_nearest_list_offsets_scratch_bytes(self.P, q)) if Q else None
+            args = (_lib.ptr(self.index), self.index.numel(), self.P, _lib.ptr(tmp), 0 if tmp is None else tmp.numel(),
+                    queries.data_ptr() if Q else None, Q, r2.data_ptr() if Q else None, _lib.ptr(exclude))
+            _lib.check(L.hidegs_nearest_list_offsets(*args, starts.data_ptr(), info.data_ptr(), stream), "nearest_list_offsets")
+            if capacity is None:
+                lo, hi = (int(v) & 0xFFFFFFFF for v in info[:2].tolist())  # the one host read
+                capacity = (hi << 32) | lo
+                if capacity > _MAX:
+                    raise RuntimeError(f"nearest: the lists hold {capacity} entries, more than 2^31 - 1: use a smaller radius "
+                                       f"or fewer queries per call")
+            rows, d2 = out if out is not None else (torch.empty(capacity, dtype=torch.int32, device=self.device),
+                                                    torch.empty(capacity, dtype=torch.float32, device=self.device)
+                                                    if distances else None)
+            _lib.check(L.hidegs_nearest_list_fill(*args, starts.data_ptr(), capacity, _lib.ptr(rows), _lib.ptr(d2), stream),
+                       "nearest_list_fill")
+        return NeighborLists(starts, rows, d2, info)
+
+
+class NeighborLists:
+    """CSR neighbour lists (NearestIndex.lists_within): the list of query j is rows[starts[j]:starts[j + 1]], with
+    d2[...] its squared distances (None without distances).  starts (Q + 1,) int32, rows int32, d2 float32, and
+    info, a (4,) int32 device tensor whose words read as unsigned are {entries of all lists mod 2^32, that number's
+    high word, the longest list, the number of non-empty lists}.  With a capacity below the number of entries, rows
+    and d2 end at the capacity and starts still holds the full spans."""
+
+    def __init__(self, starts: torch.Tensor, rows: torch.Tensor, d2, info: torch.Tensor):
+        self.starts, self.rows, self.d2, self.info = starts, rows, d2, info
+
+    def counts(self) -> torch.Tensor:
+        """(Q,) int32: the length of every list."""
+        return self.starts[1:] - self.starts[:-1]
+
+    def query_of(self) -> torch.Tensor:
+        """(len(rows),) int64: the query of every entry -- with rows, the COO / edge-list form.  No synchronisation."""
+        at = torch.arange(self.rows.numel(), dtype=torch.int32, device=self.rows.device)
+        return torch.searchsorted(self.starts[1:], at, right=True)
+
+
+def lists_within(points: torch.Tensor, queries: torch.Tensor, r2, exclude: torch.Tensor = None, capacity: int = None,
+                 distances: bool = True) -> NeighborLists:
+    """NearestIndex(points).lists_within(queries, r2, exclude, capacity, distances)."""
+    return NearestIndex(points).lists_within(queries, r2, exclude, capacity, distances)
 
 
 def nearest(points: torch.Tensor, queries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1,7 +1,10 @@
 """Oracles of the k-nearest query (include/hidegs_nearest_k.h).  Test infrastructure, no test here.
 
-exact_k_on(): the bit-exact answer by torch on a device, for inputs whose fp32 arithmetic is exact (small
-              integers and half-integers): nearest_oracle.exact_on's packed keys under torch.topk.
+exact_k_on(): the bit-exact answer by torch on a device: packed keys bits(d) << 32 | row under torch.topk.  The
+              distance is nearest_oracle's plain form, for inputs whose fp32 arithmetic is exact (small integers
+              and half-integers), or with rounded=True its rounded form, the contract's expression in every bit
+              for any input.  candidate_keys() is the rule both share with the radius oracles: which rows are
+              candidates of which query.
 check_k():    every slot of every query against float64 brute force over all points, with nearest_oracle's
               bounds.  The argument for slot i: the i + 1 truly nearest candidates all have fp32 distances of at
               most D(i)(1 + 5u), so the kernel's i-th smallest fp32 distance is no larger, and the float64
@@ -10,10 +13,7 @@ check_k():    every slot of every query against float64 brute force over all poi
 import numpy as np
 import torch
 
-from nearest_oracle import DIST_SLACK, WINNER_SLACK, _f64
-
-NAN_HI = 0x7FC00000
-INF_HI = 0x7F800000
+from nearest_oracle import DIST_SLACK, INF_HI, NAN_HI, WINNER_SLACK, _f64, distance_bits, pair_chunk
 
 
 def _exclude_on(exclude, Q, device):
@@ -24,36 +24,55 @@ def _exclude_on(exclude, Q, device):
     return e.to(device=device, dtype=torch.int64)
 
 
-def exact_k_on(points, queries, k, exclude=None, device="cpu"):
+def cloud_on(points, queries, device):
+    """(p, q): both as (n, 3) float32 tensors on `device` (copies: the cases are read-only), every row of p with a
+    non-finite coordinate as three NaNs -- its distance is a NaN from every query."""
+    p = torch.from_numpy(np.array(points, dtype=np.float32).reshape(-1, 3)).to(device)
+    q = torch.from_numpy(np.array(queries, dtype=np.float32).reshape(-1, 3)).to(device)
+    if p.shape[0]:
+        p = torch.where(torch.isfinite(p).all(1)[:, None], p, torch.full_like(p, float("nan")))
+    return p, q
+
+
+def candidate_bits(rounded, p, qq, rowid, ex):
+    """(len(qq), len(p)) int64, the high word of every key: the distance's bits from query to point in the form asked
+    for, and NAN_HI -- above INF_HI, the largest bits a candidate has, and so above every real key and every
+    radius -- for the rows that are no candidates of the query: those with a non-finite coordinate (cloud_on) and
+    the one the query excludes.  rowid: the row of every column of p; ex: the excluded row of every query of qq."""
+    hi = distance_bits(rounded)(p, qq)  # d >= 0: the bits ascend
+    return torch.where(rowid[None, :] == ex[:, None], NAN_HI, hi)
+
+
+def smallest_keys(hi, rowid, kk, answered):
+    """(idx (n, kk) int32, d2 (n, kk) float32): the kk smallest keys hi << 32 | row of every query, ascending, as
+    rows and distances; -1 / +inf where the key is no candidate's, and in every slot of a query that is not
+    `answered`."""
+    best = torch.topk((hi << 32) | rowid[None, :], kk, dim=1, largest=False, sorted=True).values
+    ok = ((best >> 32) <= INF_HI) & answered[:, None]
+    return (torch.where(ok, best & 0xFFFFFFFF, -1).to(torch.int32),
+            torch.where(ok, (best >> 32).to(torch.int32).view(torch.float32), float("inf")))
+
+
+def exact_k_on(points, queries, k, exclude=None, device="cpu", rounded=False):
     """(idx (Q, k) int32, d2 (Q, k) float32) as numpy arrays: per query the k smallest keys
     bits(d) << 32 | row, ascending.  The excluded row and the rows with a non-finite coordinate get a NaN's
     bits as their distance, above +inf's: they fill the slots no candidate takes and are reported as -1 / +inf,
-    as are the slots past P and every slot of a non-finite query."""
-    p = torch.from_numpy(np.array(points, dtype=np.float32).reshape(-1, 3)).to(device)  # copies: the cases are read-only
-    q = torch.from_numpy(np.array(queries, dtype=np.float32).reshape(-1, 3)).to(device)
+    as are the slots past P and every slot of a non-finite query.  rounded: the form of the distance
+    (nearest_oracle.distance_bits)."""
+    p, q = cloud_on(points, queries, device)
     P, Q = p.shape[0], q.shape[0]
     idx = torch.full((Q, k), -1, dtype=torch.int32, device=device)
     d2 = torch.full((Q, k), float("inf"), dtype=torch.float32, device=device)
     if P == 0 or Q == 0:
         return idx.cpu().numpy(), d2.cpu().numpy()
     ex = _exclude_on(exclude, Q, device)
-    p = torch.where(torch.isfinite(p).all(1)[:, None], p, torch.full_like(p, float("nan")))
     rows = torch.arange(P, dtype=torch.int64, device=device)
-    nan_hi = torch.tensor(NAN_HI, dtype=torch.int64, device=device)
     kk = min(k, P)
-    chunk = max(1, 60_000_000 // P)
+    chunk = pair_chunk(P, rounded, device)
     for a in range(0, Q, chunk):
         qq = q[a:a + chunk]
-        dx = p[None, :, 0] - qq[:, None, 0]
-        dy = p[None, :, 1] - qq[:, None, 1]
-        dz = p[None, :, 2] - qq[:, None, 2]
-        d = dz * dz + (dx * dx + dy * dy)
-        hi = torch.where(torch.isnan(d) | (rows[None, :] == ex[a:a + chunk, None]), nan_hi,
-                         d.view(torch.int32).to(torch.int64))  # d >= 0: the bits ascend
-        best = torch.topk((hi << 32) | rows[None, :], kk, dim=1, largest=False, sorted=True).values
-        ok = ((best >> 32) <= INF_HI) & torch.isfinite(qq).all(1)[:, None]
-        idx[a:a + chunk, :kk] = torch.where(ok, best & 0xFFFFFFFF, -1).to(torch.int32)
-        d2[a:a + chunk, :kk] = torch.where(ok, (best >> 32).to(torch.int32).view(torch.float32), float("inf"))
+        hi = candidate_bits(rounded, p, qq, rows, ex[a:a + chunk])
+        idx[a:a + chunk, :kk], d2[a:a + chunk, :kk] = smallest_keys(hi, rows, kk, torch.isfinite(qq).all(1))
     return idx.cpu().numpy(), d2.cpu().numpy()
 
 

@@ -1,9 +1,10 @@
 """Oracles of the neighbour lists (include/hidegs_nearest_lists.h).  Test infrastructure, no test here.
 
-exact_lists_on(): the bit-exact lists by torch on a device, for inputs whose fp32 arithmetic is exact (small
-                  integers and half-integers): nearest_within_oracle.exact_within_on's predicate, bits(d) <=
-                  bits(r2 + 0.0f) and r2 >= 0 over the finite rows without the excluded one, with every list in
-                  the order of `order` (the row at every position of the index; None: ascending row).
+exact_lists_on(): the bit-exact lists by torch on a device: nearest_within_oracle.exact_within_on's predicate,
+                  bits(d) <= bits(r2 + 0.0f) and r2 >= 0 over the finite rows without the excluded one, with every
+                  list in the order of `order` (the row at every position of the index; None: ascending row).  The
+                  distance is the plain form, for inputs whose fp32 arithmetic is exact (small integers and
+                  half-integers), or with rounded=True the contract's expression in every bit for any input.
 check_lists():    for inputs that round, against float64 brute force D over all points with s = 2^-20
                   (nearest_oracle's WINNER_SLACK): every row with D <= r2 (1 - s) is in its list, none with
                   D > r2 (1 + s) is, each row at most once, and every reported distance is within 2^-21 of D.
@@ -12,15 +13,15 @@ split():          the lists of a CSR triple as a Python list of (rows, d2 bits) 
 import numpy as np
 import torch
 
-from nearest_k_oracle import NAN_HI, _exclude_on
-from nearest_oracle import DIST_SLACK, WINNER_SLACK, _f64
-from nearest_within_oracle import _r2_on
+from nearest_k_oracle import _exclude_on, candidate_bits, cloud_on
+from nearest_oracle import DIST_SLACK, WINNER_SLACK, _f64, pair_chunk
+from nearest_within_oracle import _r2_on, in_range, radius_bits
 
 
-def exact_lists_on(points, queries, r2, exclude=None, order=None, device="cpu"):
-    """(starts (Q + 1,) int64, rows (M,) int32, d2 (M,) float32) as numpy arrays."""
-    p = torch.from_numpy(np.array(points, dtype=np.float32).reshape(-1, 3)).to(device)
-    q = torch.from_numpy(np.array(queries, dtype=np.float32).reshape(-1, 3)).to(device)
+def exact_lists_on(points, queries, r2, exclude=None, order=None, device="cpu", rounded=False):
+    """(starts (Q + 1,) int64, rows (M,) int32, d2 (M,) float32) as numpy arrays.  rounded: the form of the
+    distance (nearest_oracle.distance_bits)."""
+    p, q = cloud_on(points, queries, device)
     P, Q = p.shape[0], q.shape[0]
     starts = np.zeros(Q + 1, dtype=np.int64)
     if P == 0 or Q == 0:
@@ -29,25 +30,17 @@ def exact_lists_on(points, queries, r2, exclude=None, order=None, device="cpu"):
         torch.as_tensor(np.asarray(order)).to(device=device, dtype=torch.int64)
     assert rowid.shape == (P,)
     p = p[rowid]  # column c of everything below is position c of the order
-    r = _r2_on(r2, Q, device)
-    rb = torch.where((r >= 0) & torch.isfinite(q).all(1), (r + 0.0).view(torch.int32).to(torch.int64), -1)
+    rb = radius_bits(_r2_on(r2, Q, device), q)
     ex = _exclude_on(exclude, Q, device)
-    p = torch.where(torch.isfinite(p).all(1)[:, None], p, torch.full_like(p, float("nan")))
-    nan_hi = torch.tensor(NAN_HI, dtype=torch.int64, device=device)
     counts, rows, d2 = [], [], []
-    chunk = max(1, 40_000_000 // P)
+    chunk = pair_chunk(P, rounded, device)
     for a in range(0, Q, chunk):
-        qq = q[a:a + chunk]
-        dx = p[None, :, 0] - qq[:, None, 0]
-        dy = p[None, :, 1] - qq[:, None, 1]
-        dz = p[None, :, 2] - qq[:, None, 2]
-        d = dz * dz + (dx * dx + dy * dy)
-        hi = torch.where(torch.isnan(d) | (rowid[None, :] == ex[a:a + chunk, None]), nan_hi, d.view(torch.int32).to(torch.int64))
-        inr = hi <= rb[a:a + chunk, None]
+        hi = candidate_bits(rounded, p, q[a:a + chunk], rowid, ex[a:a + chunk])
+        inr = in_range(hi, rb[a:a + chunk])
         counts.append(inr.sum(1).cpu().numpy())
         at = torch.nonzero(inr)  # row-major: by query, then by position
         rows.append(rowid[at[:, 1]].to(torch.int32).cpu().numpy())
-        d2.append(d[at[:, 0], at[:, 1]].cpu().numpy())
+        d2.append(hi[at[:, 0], at[:, 1]].to(torch.int32).view(torch.float32).cpu().numpy())
     starts[1:] = np.cumsum(np.concatenate(counts))
     return starts, np.concatenate(rows), np.concatenate(d2)
 

@@ -1,8 +1,10 @@
 """Oracles of the fixed-radius query (include/hidegs_nearest_within.h).  Test infrastructure, no test here.
 
-exact_within_on(): the bit-exact answer by torch on a device, for inputs whose fp32 arithmetic is exact (small
-                   integers and half-integers): nearest_k_oracle.exact_k_on's packed keys bits(d) << 32 | row with
-                   the contract's in-range test, bits(d) <= bits(r2 + 0.0f) and r2 >= 0.
+exact_within_on(): the bit-exact answer by torch on a device: nearest_k_oracle.exact_k_on's packed keys
+                   bits(d) << 32 | row with the contract's in-range test, bits(d) <= bits(r2 + 0.0f) and r2 >= 0
+                   (radius_bits, in_range).  The distance is the plain form, for inputs whose fp32 arithmetic is
+                   exact (small integers and half-integers), or with rounded=True the contract's expression in
+                   every bit for any input.
 check_within():    for inputs that round, against float64 brute force D over all points with s = 2^-20,
                    nearest_oracle's WINNER_SLACK: an fp32 d is within 2^-21 of D relatively, so a row with
                    D <= r2 (1 - s) is in range, one with D > r2 (1 + s) is not, and the rows between may be either.
@@ -10,8 +12,8 @@ check_within():    for inputs that round, against float64 brute force D over all
 import numpy as np
 import torch
 
-from nearest_k_oracle import INF_HI, NAN_HI, _exclude_on
-from nearest_oracle import DIST_SLACK, WINNER_SLACK, _f64
+from nearest_k_oracle import _exclude_on, candidate_bits, cloud_on, smallest_keys
+from nearest_oracle import DIST_SLACK, NAN_HI, WINNER_SLACK, _f64, pair_chunk
 
 MAX_COUNT = 2 ** 31 - 1
 
@@ -25,45 +27,45 @@ def _r2_on(r2, Q, device):
     return t.expand(Q).contiguous() if t.dim() == 0 else t.reshape(Q)
 
 
-def exact_within_on(points, queries, r2, k, max_count=None, exclude=None, device="cpu"):
+def radius_bits(r, q):
+    """(Q,) int64: bits(r2 + 0.0f) of every query's squared radius r (float32) where r2 >= 0 -- the sign of -0 is
+    cleared in the bits themselves, so that a denormal radius stays what it is on every device -- and -1, below
+    every distance's bits, where nothing is in range: a negative or NaN radius, a non-finite query q."""
+    return torch.where((r >= 0) & torch.isfinite(q).all(1), (r.view(torch.int32) & 0x7FFFFFFF).to(torch.int64), -1)
+
+
+def in_range(hi, rb):
+    """The contract's inclusive test on candidate_bits: bits(d) <= bits(r2 + 0.0f).  NAN_HI, of the rows that are
+    no candidates, is above +inf's bits, the largest radius."""
+    return hi <= rb[:, None]
+
+
+def exact_within_on(points, queries, r2, k, max_count=None, exclude=None, device="cpu", rounded=False):
     """(count (Q,) int32, idx (Q, k) int32, d2 (Q, k) float32) as numpy arrays: per query the number of keys in
     range, capped at max_count, and the k smallest of them, ascending; -1 / +inf past them.  The excluded row and
-    the rows with a non-finite coordinate get a NaN's bits as their distance, above every radius's."""
+    the rows with a non-finite coordinate get a NaN's bits as their distance, above every radius's.  rounded: the
+    form of the distance (nearest_oracle.distance_bits)."""
     max_count = MAX_COUNT if max_count is None else max_count
-    p = torch.from_numpy(np.array(points, dtype=np.float32).reshape(-1, 3)).to(device)  # copies: the cases are read-only
-    q = torch.from_numpy(np.array(queries, dtype=np.float32).reshape(-1, 3)).to(device)
+    p, q = cloud_on(points, queries, device)
     P, Q = p.shape[0], q.shape[0]
     count = torch.zeros(Q, dtype=torch.int32, device=device)
     idx = torch.full((Q, k), -1, dtype=torch.int32, device=device)
     d2 = torch.full((Q, k), float("inf"), dtype=torch.float32, device=device)
     if P == 0 or Q == 0:
         return count.cpu().numpy(), idx.cpu().numpy(), d2.cpu().numpy()
-    r = _r2_on(r2, Q, device)
-    # bits(r2 + 0.0f) where r2 >= 0; -1 where nothing is in range (a negative or NaN radius, a non-finite query)
-    rb = torch.where((r >= 0) & torch.isfinite(q).all(1), (r + 0.0).view(torch.int32).to(torch.int64), -1)
+    rb = radius_bits(_r2_on(r2, Q, device), q)
     ex = _exclude_on(exclude, Q, device)
-    p = torch.where(torch.isfinite(p).all(1)[:, None], p, torch.full_like(p, float("nan")))
     rows = torch.arange(P, dtype=torch.int64, device=device)
-    nan_hi = torch.tensor(NAN_HI, dtype=torch.int64, device=device)
     kk = min(k, P)
-    chunk = max(1, 60_000_000 // P)
+    chunk = pair_chunk(P, rounded, device)
     for a in range(0, Q, chunk):
-        qq = q[a:a + chunk]
-        dx = p[None, :, 0] - qq[:, None, 0]
-        dy = p[None, :, 1] - qq[:, None, 1]
-        dz = p[None, :, 2] - qq[:, None, 2]
-        d = dz * dz + (dx * dx + dy * dy)
-        hi = torch.where(torch.isnan(d) | (rows[None, :] == ex[a:a + chunk, None]), nan_hi,
-                         d.view(torch.int32).to(torch.int64))  # d >= 0: the bits ascend
-        inr = hi <= rb[a:a + chunk, None]  # NAN_HI is above +inf's bits, the largest radius
+        hi = candidate_bits(rounded, p, q[a:a + chunk], rows, ex[a:a + chunk])
+        inr = in_range(hi, rb[a:a + chunk])
         count[a:a + chunk] = inr.sum(1).clamp(max=max_count).to(torch.int32)
         if kk == 0:
             continue
-        hi = torch.where(inr, hi, nan_hi)
-        best = torch.topk((hi << 32) | rows[None, :], kk, dim=1, largest=False, sorted=True).values
-        ok = (best >> 32) <= INF_HI
-        idx[a:a + chunk, :kk] = torch.where(ok, best & 0xFFFFFFFF, -1).to(torch.int32)
-        d2[a:a + chunk, :kk] = torch.where(ok, (best >> 32).to(torch.int32).view(torch.float32), float("inf"))
+        hi = torch.where(inr, hi, NAN_HI)  # out of range: no candidate of the list
+        idx[a:a + chunk, :kk], d2[a:a + chunk, :kk] = smallest_keys(hi, rows, kk, rb[a:a + chunk] >= 0)
     return count.cpu().numpy(), idx.cpu().numpy(), d2.cpu().numpy()
 
 

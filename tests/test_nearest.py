@@ -250,6 +250,45 @@ def test_the_float64_form_of_fmaf_equals_libm_in_every_bit():
     assert (twice.view(np.uint32) != exp.view(np.uint32)).sum() > 500, "the cases were to include double roundings"
 
 
+def libm_fmaf(a, b, c):
+    import ctypes.util
+    libm = ctypes.CDLL(ctypes.util.find_library("m"))
+    libm.fmaf.restype = ctypes.c_float
+    libm.fmaf.argtypes = [ctypes.c_float] * 3
+    return np.array([libm.fmaf(x, y, z) for x, y, z in zip(a.tolist(), b.tolist(), c.tolist())], dtype=np.float32)
+
+
+@pytest.mark.parametrize("ends", ["overflow", "underflow"])
+def test_the_float64_form_of_fmaf_equals_libm_at_both_ends_of_the_float_range(ends):
+    """Products and addends of 2^110 to 2^128, whose sums overflow to +-inf or stay just below, and of 2^-149 to
+    2^-120, whose sums are denormal, zero or just normal -- a squared distance is such a sum at both ends.  The
+    factors are drawn so that the product has the magnitude asked for; half of the addends have the other sign."""
+    g = np.random.default_rng(10 if ends == "overflow" else 11)
+    n = 20_000
+    lo, hi = (110, 128) if ends == "overflow" else (-149, -120)
+
+    def magnitude():
+        return (1.0 + g.random(n)) * 2.0 ** g.uniform(lo, hi, n)
+
+    prod, add = magnitude(), magnitude()
+    split = g.uniform(0.3, 0.7, n)  # the product's exponent, shared between the factors: both are normal fp32 values
+    a = (np.abs(prod) ** split).astype(np.float32)
+    b = (np.abs(prod) ** (1.0 - split)).astype(np.float32)
+    with np.errstate(over="ignore"):
+        c = (add * np.where(g.random(n) < 0.5, 1.0, -1.0)).astype(np.float32)  # above FLT_MAX: an infinite addend
+        b = np.where(g.random(n) < 0.25, -b, b)
+    exp = libm_fmaf(a, b, c)
+    got = nearest_oracle.fma32(a.astype(np.float64), b.astype(np.float64), c.astype(np.float64))
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), exp.view(np.uint32))
+    tiny = np.finfo(np.float32).tiny
+    ninf, nzero, nden = int(np.isinf(exp).sum()), int((exp == 0).sum()), int(((exp != 0) & (np.abs(exp) < tiny)).sum())
+    print(f"{ends}: {ninf} infinite, {nden} denormal, {nzero} zero of {n}")
+    if ends == "overflow":
+        assert ninf > 200 and np.isfinite(exp).sum() > n // 2 and np.isfinite(c[np.isinf(exp)]).sum() > 100
+    else:
+        assert nden > n // 2 and nzero > 10 and (np.abs(exp) >= tiny).sum() > 100
+
+
 def test_the_rounded_oracle_equals_the_exact_one_where_nothing_rounds():
     g = np.random.default_rng(5)
     pts = g.integers(0, 6, (700, 3)).astype(np.float32)  # many duplicates and ties

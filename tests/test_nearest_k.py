@@ -223,3 +223,43 @@ def test_check_k_accepts_the_exact_answer_and_rejects_wrong_ones():
     for cloud in (none, none[:0]):
         i, d = nearest_k_oracle.exact_k_on(cloud, qs, 3)
         assert (i == -1).all() and nearest_k_oracle.check_k(cloud, qs, 3, None, i, d) == 0
+
+
+# ---- the rounded form against an independent implementation -------------------------------------------------
+def anchor_cloud(name):
+    """The clouds of distCUDA2's every-point tests (knn_clouds): the base cloud at five scales that leave the normal
+    range, the degenerate sets (the first 6,000 rows of the three largest: both sides are brute force) and the cube
+    at 2^20."""
+    import knn_clouds as kc
+    if isinstance(name, int):
+        return kc.range_scaled(name)
+    if name == "offset_cube":
+        return kc.offset_cube(5_000)
+    return kc.degenerate(name)[:6_000]
+
+
+def mean3_of(d2):
+    with np.errstate(over="ignore"):
+        return ((d2[:, 0] + d2[:, 1]) + d2[:, 2]) / np.float32(3.0)
+
+
+@pytest.mark.parametrize("name", [66, 68, -60, -66, -70, "duplicates", "identical", "line", "plane", "ties_grid",
+                                  "two_far_clusters", "offset_cube"])
+def test_the_rounded_three_nearest_are_the_c_oracle_in_every_bit(oracle_lib, name):
+    """exact_k_on(rounded=True) and oracle.knn_mean3 (knn_ref.c) share no code: the first reproduces fmaf's one
+    rounding in float64 tensors, the second calls it.  Their means of the three nearest distances without self agree
+    in every bit where distances overflow (the C oracle's list starts at FLT_MAX, which an infinite distance does
+    not replace; on these clouds a sum with FLT_MAX in it overflows like one with +inf), where they are denormal or
+    zero, and where thousands tie.  The order among equal distances does not reach a mean, and is the lattices' to check."""
+    import knn_clouds as kc
+    pts = anchor_cloud(name)
+    P = len(pts)
+    idx, d2 = nearest_k_oracle.exact_k_on(pts, pts, 3, exclude=np.arange(P, dtype=np.int32), device="cpu", rounded=True)
+    assert (idx >= 0).all() and (idx != np.arange(P)[:, None]).all()
+    got, exp = mean3_of(d2), oracle_lib.knn_mean3(pts)
+    bad = np.flatnonzero(got.view(np.uint32) != exp.view(np.uint32))
+    assert bad.size == 0, f"{name}: {bad.size} of {P} differ, first {bad[:5]}: {got[bad[:5]]} against {exp[bad[:5]]}"
+    if isinstance(name, int):
+        assert kc.result_classes(got) == kc.RANGE_CLASSES[name]
+    if name in ("identical", "duplicates"):
+        assert (d2[:, 0] == 0).sum() == (P if name == "identical" else 2 * 1_500 + 700)

@@ -333,3 +333,22 @@ def test_check_lists_accepts_the_exact_answer_and_rejects_wrong_ones():
         else:
             with pytest.raises(AssertionError, match="are missing|outside the radius"):
                 nlo.check_lists(*args)
+
+
+def test_the_rounded_oracle_equals_the_exact_one_where_nothing_rounds():
+    """The two forms of the distance under the one selection rule, on test_nearest_within's exact inputs, in the row
+    order and in a shuffled one; the counts are the count oracle's."""
+    import nearest_within_oracle
+    from test_nearest_within import exact_inputs
+    pts, qs, r2, ex = exact_inputs(7)
+    order = np.random.default_rng(7).permutation(len(pts))
+    for exclude, o in ((None, None), (ex, None), (ex, order)):
+        a = nlo.exact_lists_on(pts, qs, r2, exclude, o)
+        b = nlo.exact_lists_on(pts, qs, r2, exclude, o, rounded=True)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32))
+        count = nearest_within_oracle.exact_within_on(pts, qs, r2, 0, None, exclude, rounded=True)[0]
+        assert np.array_equal(np.diff(a[0]), count) and count.max() >= np.isfinite(pts).all(1).sum() - 1 and (count == 0).sum() > 100
+    pos = np.empty(len(pts), dtype=np.int64)
+    pos[order] = np.arange(len(pts))
+    for rows, _ in nlo.split(*b):
+        assert (np.diff(pos[rows]) > 0).all()

@@ -290,3 +290,50 @@ def test_check_within_accepts_the_exact_answer_and_rejects_wrong_ones():
     for cloud in (nan, nan[:0]):
         got = ew(cloud, qs, np.inf, 3)
         assert (got[0] == 0).all() and (got[1] == -1).all() and cw(cloud, qs, np.inf, 3, None, None, *got) == (0, 0)
+
+
+def exact_inputs(seed):
+    """Small integers and halves with many duplicates and ties, some rows and queries not finite, one radius per
+    query from values that hit the distances exactly, and an excluded row for two queries in three."""
+    g = np.random.default_rng(seed)
+    pts = g.integers(0, 6, (700, 3)).astype(np.float32)
+    pts[g.integers(0, 700, 30), g.integers(0, 3, 30)] = np.array([np.nan, np.inf, -np.inf], dtype=np.float32)[g.integers(0, 3, 30)]
+    qs = (g.integers(-4, 16, (900, 3)) * 0.5).astype(np.float32)
+    qs[5, 1] = np.nan
+    qs[6, 0] = -np.inf
+    r2 = np.array([0.0, -0.0, 0.25, 0.75, 1.0, 2.75, 9.0, 40.0, np.inf, -1.0, np.nan], dtype=np.float32)[g.integers(0, 11, 900)]
+    ex = np.where(np.arange(900) % 3 == 0, -1, g.integers(0, 700, 900)).astype(np.int32)
+    return pts, qs, r2, ex
+
+
+def test_the_rounded_oracle_equals_the_exact_one_where_nothing_rounds():
+    """The two forms of the distance under the one selection rule, as test_nearest's test of the same name does
+    for the k nearest; and exact_k_on itself, the rule with exclusion."""
+    pts, qs, r2, ex = exact_inputs(6)
+    for k, max_count, exclude in ((0, None, None), (5, None, ex), (64, 7, ex), (64, None, None)):
+        a = nearest_within_oracle.exact_within_on(pts, qs, r2, k, max_count, exclude)
+        b = nearest_within_oracle.exact_within_on(pts, qs, r2, k, max_count, exclude, rounded=True)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32))
+    assert a[0].max() == np.isfinite(pts).all(1).sum() < 700 and (a[0] == 0).sum() > 100 and (a[1][:, -1] >= 0).sum() > 100  # every candidate, none, full lists
+    for k, exclude in ((3, None), (17, ex)):
+        a = nearest_k_oracle.exact_k_on(pts, qs, k, exclude)
+        b = nearest_k_oracle.exact_k_on(pts, qs, k, exclude, rounded=True)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
+    assert (a[0][[5, 6]] == -1).all() and (a[0][np.arange(900) != 5][1:] >= 0).sum() > 0
+
+
+def test_a_denormal_radius_and_the_radius_bits():
+    """radius_bits is bits(r2 + 0.0f) without the addition: a denormal radius keeps its bits, -0 is 0."""
+    r = torch.tensor([0.0, -0.0, 1e-45, 1e-40, 1.0, np.inf, -1e-45, np.nan, 1.0], dtype=torch.float32)
+    q = torch.zeros((9, 3))
+    q[8, 0] = np.inf
+    assert nearest_within_oracle.radius_bits(r, q).tolist() == [0, 0, 1, 71362, 0x3F800000, 0x7F800000, -1, -1, -1]
+    # two points 2^-75 apart: the squared distance is 2^-150, which rounds to even, 0; three times that apart: 9 * 2^-150 is 4.5
+    # denormal steps, which rounds to 4
+    pts = np.zeros((3, 3), dtype=np.float32)
+    pts[1, 0], pts[2, 0] = 2.0 ** -75, 3 * 2.0 ** -75
+    qs = np.zeros((4, 3), dtype=np.float32)
+    r2 = np.array([0.0, 4e-45, 5.6e-45, np.inf], dtype=np.float32).view(np.uint32)
+    assert r2.tolist() == [0, 3, 4, 0x7F800000]
+    count, idx, d2 = nearest_within_oracle.exact_within_on(pts, qs, r2.view(np.float32), 3, rounded=True)
+    assert count.tolist() == [2, 2, 3, 3] and idx[2].tolist() == [0, 1, 2] and d2[2].view(np.uint32).tolist() == [0, 0, 4]

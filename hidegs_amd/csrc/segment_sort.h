@@ -37,23 +37,36 @@ __device__ __forceinline__ void seg_load(const uint64_t* __restrict__ src_k, con
                                          uint32_t& hd)
 {
     const int t = threadIdx.x;
+    uint2 rec[kSegItems];  // Packed: the records as loaded (not Packed: unused, k and v are loaded as they are)
+    // First pass: the loads alone, all of a thread's items in flight together.
 #pragma unroll
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = t + q * kBlock;
         if (i < m) {
             if (Packed) {
-                const uint2 rec = reinterpret_cast<const uint2*>(src_k)[begin + i];
-                k[q] = ((uint64_t)ref_hi << 32) | rec.x;
-                v[q] = rec.y;
+                rec[q] = reinterpret_cast<const uint2*>(src_k)[begin + i];
             } else {
                 k[q] = src_k[begin + i];
                 v[q] = src_v[begin + i];
             }
-            const uint32_t x = (uint32_t)k[q];
-            lo = min(lo, x);
-            hi = max(hi, x);
-            if (!Packed) hd |= (uint32_t)(k[q] >> 32) ^ ref_hi;
         }
+    }
+    // Second pass: every use of a loaded value -- the Packed key and value formed from the record, MIN / MAX, hd.
+    // In the load's own branch a use, even the move that forms a Packed key, puts a wait for item q's load in
+    // front of item q + 1's: eight global round trips in a row where one is enough.  A thread without item q has
+    // no later item either: the pass ends there, so rec[q] of an absent item, which was never written, is never
+    // read, and a short segment's waves do not test eight masks a second time.
+#pragma unroll
+    for (int q = 0; q < kSegItems; q++) {
+        if (t + q * kBlock >= m) break;
+        if (Packed) {
+            k[q] = ((uint64_t)ref_hi << 32) | rec[q].x;
+            v[q] = rec[q].y;
+        }
+        const uint32_t x = (uint32_t)k[q];
+        lo = min(lo, x);
+        hi = max(hi, x);
+        if (!Packed) hd |= (uint32_t)(k[q] >> 32) ^ ref_hi;
     }
 }
 

@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI in include/hidegs.h, include/hidegs_rows.h, include/hidegs_resize.h,
 include/hidegs_clone.h, include/hidegs_topk.h, include/hidegs_nearest.h, include/hidegs_nearest_k.h,
-include/hidegs_nearest_within.h, include/hidegs_nearest_lists.h and include/hidegs_voxel.h
-(hidegs_amd/libhidegs.so).
+include/hidegs_nearest_within.h, include/hidegs_nearest_lists.h, include/hidegs_voxel.h and
+include/hidegs_moments.h (hidegs_amd/libhidegs.so).
 
 This is the only place that loads the native library.  It fails loudly: a missing
 library raises ImportError-like RuntimeError at first use, and a non-zero return
@@ -172,14 +172,22 @@ VOXEL_SIGNATURES = {
     "hidegs_voxel_reduce_rows": (I, [P, SZ, P, I, P, P, P, LL, LL, P, P]),
 }
 
+# include/hidegs_moments.h, in its order
+MOMENTS_SIGNATURES = {
+    "hidegs_neighbor_moments_scratch_bytes": (SZ, [LL]),
+    "hidegs_neighbor_moments_table": (I, [P, P, LL, P, LL, I, P, P, P, P, P, P]),
+    "hidegs_neighbor_moments_lists": (I, [P, SZ, P, P, LL, P, P, LL, LL, P, P, P, P, P, P]),
+    "hidegs_sym3_eigen": (I, [P, P, P, LL, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
 
 def load_library(path: str) -> C.CDLL:
     """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h, hidegs_resize.h,
-    hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h, hidegs_nearest_within.h, hidegs_nearest_lists.h
-    and hidegs_voxel.h bound (lib() for the product build;
+    hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h, hidegs_nearest_within.h, hidegs_nearest_lists.h,
+    hidegs_voxel.h and hidegs_moments.h bound (lib() for the product build;
     tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
@@ -187,7 +195,8 @@ def load_library(path: str) -> C.CDLL:
     dll = C.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES, **CLONE_SIGNATURES,
                               **TOPK_SIGNATURES, **NEAREST_SIGNATURES, **NEAREST_K_SIGNATURES,
-                              **NEAREST_WITHIN_SIGNATURES, **NEAREST_LISTS_SIGNATURES, **VOXEL_SIGNATURES}.items():
+                              **NEAREST_WITHIN_SIGNATURES, **NEAREST_LISTS_SIGNATURES, **VOXEL_SIGNATURES,
+                              **MOMENTS_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

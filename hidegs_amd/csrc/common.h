@@ -2,6 +2,7 @@
 // scratch carving, launch checks and a few wave64 helpers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -74,6 +75,8 @@ struct Carver {
         return p;
     }
 };
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- wave64 helpers (device) --------------------------------------------------
 constexpr int kWave = 64;
@@ -176,6 +179,34 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
     return v;
+}
+
+// Value of lane `src` (wave-uniform) as a wave-uniform (scalar-register) float.
+__device__ __forceinline__ float uniform_lane(float v, int src)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
+// Mask of the lanes below `lane`: its popcount with a ballot is the lane's rank among the set lanes.
+__device__ __forceinline__ uint64_t lanes_below(int lane) { return (lane == 0) ? 0ull : (~0ull >> (64 - lane)); }
+
+// Appends one entry per lane with `flag` to a list whose length is *counter: one ballot, one atomic by lane 0,
+// the base handed on by readfirstlane, every flagged lane its own slot in lane order.  Returns the caller's
+// slot, valid where `flag` holds.  Every lane of the wave must be active.
+__device__ __forceinline__ uint32_t wave_append(bool flag, uint32_t* counter)
+{
+    const uint64_t m = __ballot(flag);
+    if (!m) return 0;
+    const int lane = lane_id();
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    return base + (uint32_t)__popcll(m & lanes_below(lane));
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z)
+{
+    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for a NaN
 }
 
 }  // namespace hidegs

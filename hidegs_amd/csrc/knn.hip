@@ -14,7 +14,8 @@
 // in the oracle: the contraction an LLVM-based CUDA compiler gives that expression (the left product
 // of `a*b + c*d` fused; DESIGN.md "Parity").
 //
-// Search (MI355X-first):
+// Search (MI355X-first).  Steps 1, 2 and 4, the distance and the lower bounds are morton_tree.h's, which
+// the nearest-point index (nearest.hip) builds and prunes with as well:
 //   1. bounding box (grid-stride partial min/max + one finishing workgroup) -- no host
 //      sync; the reference does two blocking D2H copies (simple_knn.cu:194-201);
 //   2. 48-bit Morton codes (16 bits/axis), stable LSD radix sort (primitives.hip);
@@ -37,6 +38,7 @@
 
 #include "common.h"
 #include "knn_stats.h"
+#include "morton_tree.h"
 
 namespace hidegs {
 
@@ -44,45 +46,15 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;  // 4 waves = 4 leaves per workgroup
-constexpr int kLeaf = 64;               // points per leaf
-constexpr int kFan = 64;                // leaves per super-box
 constexpr int kSub = 4;                 // sub-boxes per leaf (16 points each): the fine filter
-// Per axis; the sort runs over all 3x these bits.  10 bits sort in 4 passes instead of 6 but the coarser
-// order costs the search as much; a sort over the high bits only loses the dense region of a cloud whose
-// outliers inflate the bounding box.
-constexpr int kMortonBits = 16;
-constexpr int kBoundBlocks = 1024;
 constexpr float kHardFactor = 8.0f;     // 3rd-best above 8x the wave mean -> phase 2
 
-struct Box {
-    float4 lo, hi;
+// distCUDA2 keys and boxes every row as it is, as the reference does (morton_tree.h).
+struct KnnTree {
+    static constexpr bool kNonFiniteLast = false;
 };
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-__device__ __forceinline__ float sqdist(float4 q, float4 c)
-{
-    const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
-    return fmaf(dz, dz, fmaf(dx, dx, dy * dy));
-}
-
-// Lower bound of sqdist(q, c) over c in the box, same monotone expression as sqdist.
-__device__ __forceinline__ float box_point_lb(const Box& b, float4 q)
-{
-    const float gx = fmaxf(fmaxf(b.lo.x - q.x, q.x - b.hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(b.lo.y - q.y, q.y - b.hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(b.lo.z - q.z, q.z - b.hi.z), 0.f);
-    return fmaf(gz, gz, fmaf(gx, gx, gy * gy));
-}
-
-// Lower bound over every query in the AABB [qlo, qhi] and every point of the box.
-__device__ __forceinline__ float box_box_lb(const Box& b, float4 qlo, float4 qhi)
-{
-    const float gx = fmaxf(fmaxf(b.lo.x - qhi.x, qlo.x - b.hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(b.lo.y - qhi.y, qlo.y - b.hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(b.lo.z - qhi.z, qlo.z - b.hi.z), 0.f);
-    return fmaf(gz, gz, fmaf(gx, gx, gy * gy));
-}
 
 // Keep the three smallest values seen (a multiset, as updateKBest<3> does).  NaN never enters.
 // Every value here is a non-negative float (a sum of squares, FLT_MAX or +inf), whose bit
@@ -102,12 +74,6 @@ __device__ __forceinline__ void kbest(float d, float& b0, float& b1, float& b2)
     b0 = __uint_as_float(t0);
 }
 
-// Value of lane `src` as a wave-uniform (scalar-register) float.
-__device__ __forceinline__ float uniform_lane(float v, int src)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
 constexpr int kChunk = kLeaf / kSub;  // points per sub-box
 
 // Evaluates the kChunk candidates held by lanes k0 .. k0 + kChunk of `c` (one point per lane) against
@@ -124,106 +90,6 @@ __device__ __forceinline__ void eval_lanes(float4 c, int k0, int nvalid, int sel
         const float d = sqdist(p, q);
         kbest((k < nvalid && k != self) ? d : FLT_MAX, b0, b1, b2);
     }
-}
-
-__device__ __forceinline__ uint64_t spread3(uint32_t v)
-{
-    // bit i of v -> bit 3i (v < 2^21)
-    uint64_t x = v & 0x1fffffu;
-    x = (x | (x << 32)) & 0x001f00000000ffffull;
-    x = (x | (x << 16)) & 0x001f0000ff0000ffull;
-    x = (x | (x << 8)) & 0x100f00f00f00f00full;
-    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
-}
-
-// ---- 1. bounds --------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void bounds_kernel(const float* __restrict__ pts, int P,
-                                                        float* __restrict__ partials)
-{
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float v = pts[3 * i + a];
-            lo[a] = fminf(lo[a], v);
-            hi[a] = fmaxf(hi[a], v);
-        }
-    }
-    __shared__ float s[kWaves][6];
-    const int wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        lo[a] = wave_min(lo[a]);
-        hi[a] = wave_max(hi[a]);
-    }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; a++) {
-            s[wave][a] = lo[a];
-            s[wave][3 + a] = hi[a];
-        }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = s[0][threadIdx.x];
-        for (int w = 1; w < kWaves; w++) v = threadIdx.x < 3 ? fminf(v, s[w][threadIdx.x]) : fmaxf(v, s[w][threadIdx.x]);
-        partials[blockIdx.x * 6 + threadIdx.x] = v;
-    }
-}
-
-// params = {lo.x, lo.y, lo.z, scale.x, scale.y, scale.z}
-__global__ __launch_bounds__(kBlock) void bounds_finalize_kernel(const float* __restrict__ partials, int nparts,
-                                                                 float* __restrict__ params)
-{
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int b = threadIdx.x; b < nparts; b += kBlock)
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], partials[b * 6 + a]);
-            hi[a] = fmaxf(hi[a], partials[b * 6 + 3 + a]);
-        }
-    __shared__ float s[kWaves][6];
-    const int wave = threadIdx.x / kWave;
-    for (int a = 0; a < 3; a++) {
-        lo[a] = wave_min(lo[a]);
-        hi[a] = wave_max(hi[a]);
-    }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; a++) {
-            s[wave][a] = lo[a];
-            s[wave][3 + a] = hi[a];
-        }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        float l = s[0][a], h = s[0][3 + a];
-        for (int w = 1; w < kWaves; w++) {
-            l = fminf(l, s[w][a]);
-            h = fmaxf(h, s[w][3 + a]);
-        }
-        const float ext = h - l;
-        const float q = (float)((1u << kMortonBits) - 1u);
-        params[a] = l;
-        params[3 + a] = (ext > 0.f && ext < INFINITY) ? q / ext : 0.f;
-    }
-}
-
-// ---- 2. Morton keys -------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void morton_kernel(const float* __restrict__ pts, int P,
-                                                        const float* __restrict__ params, uint64_t* __restrict__ keys,
-                                                        uint32_t* __restrict__ vals)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= P) return;
-    const float qmax = (float)((1u << kMortonBits) - 1u);
-    uint64_t code = 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        float t = (pts[3 * i + a] - params[a]) * params[3 + a];
-        t = fminf(fmaxf(t, 0.f), qmax);  // NaN -> 0 via fmaxf
-        code |= spread3((uint32_t)t) << a;
-    }
-    keys[i] = code;
-    vals[i] = (uint32_t)i;
 }
 
 // ---- 3./4. gather into sorted order; leaf and super boxes ---------------------------------------
@@ -261,7 +127,6 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const float* __restrict_
                                                         int P, float4* __restrict__ sp, int nleaves,
                                                         Box* __restrict__ leaves, Box* __restrict__ subs)
 {
-    static_assert(kLeaf == kWave, "one wave per leaf");
     const int j = blockIdx.x * kBlock + threadIdx.x;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     bool valid = false;
@@ -276,20 +141,6 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const float* __restrict_
     const int L = j / kLeaf;  // wave-uniform
     if (L >= nleaves) return;  // whole wave
     store_leaf_boxes(p, valid, L, lane_id(), leaves, subs);
-}
-
-__global__ __launch_bounds__(kBlock) void super_box_kernel(const Box* __restrict__ leaves, int nleaves, int nsuper,
-                                                           Box* __restrict__ supers)
-{
-    const int S = blockIdx.x * kWaves + threadIdx.x / kWave;
-    if (S >= nsuper) return;
-    const int l = S * kFan + lane_id();
-    const bool valid = l < nleaves;
-    Box b = valid ? leaves[l] : Box{make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.f), make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.f)};
-    Box r;
-    r.lo = make_float4(wave_min(b.lo.x), wave_min(b.lo.y), wave_min(b.lo.z), 0.f);
-    r.hi = make_float4(wave_max(b.hi.x), wave_max(b.hi.y), wave_max(b.hi.z), 0.f);
-    if (lane_id() == 0) supers[S] = r;
 }
 
 // ---- 5. phase 1: one wave per leaf ------------------------------------------------------------
@@ -342,20 +193,12 @@ struct KnnCounters {
 };
 static_assert(sizeof(KnnCounters) <= kAlign, "knn_stats.h finds its block one carving step behind the counters");
 
-// Mask of the lanes below `lane`: its popcount with a ballot is the lane's rank among the set lanes.
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (lane == 0) ? 0ull : (~0ull >> (64 - lane)); }
-
 // Appends query `me` of every lane with `flag` to the hard list (phase 2's input): one atomic per wave.
 __device__ __forceinline__ void push_hard(bool flag, int me, KnnCounters* __restrict__ counters,
                                           uint32_t* __restrict__ hard)
 {
-    const uint64_t m = __ballot(flag);
-    if (!m) return;
-    const int lane = lane_id();
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&counters->hard, (uint32_t)__popcll(m));
-    base = __shfl(base, 0, kWave);
-    if (flag) hard[base + __popcll(m & lanes_below(lane))] = (uint32_t)me;
+    const uint32_t at = wave_append(flag, &counters->hard);
+    if (flag) hard[at] = (uint32_t)me;
 }
 
 // At least 7 waves per SIMD set the register budget: knn_leaf 792/790 -> 773/773 us frustum against the 6
@@ -657,10 +500,7 @@ __global__ __launch_bounds__(kBlock) void knn_hard_kernel(const float4* __restri
 }
 
 struct KnnLayout {
-    uint64_t *keys, *keys_sorted;
-    uint32_t *vals, *vals_sorted;
-    void* sort_tmp;
-    size_t sort_bytes;
+    SortLayout sort;
     float4* sp;
     Box *leaves, *subs, *supers;
     uint32_t* hard;
@@ -675,12 +515,7 @@ KnnLayout layout(void* base, int P)
     const int nleaves = ceil_div(P, kLeaf), nsuper = ceil_div(nleaves, kFan);
     Carver c(base);
     KnnLayout l;
-    l.keys = c.take<uint64_t>(P);
-    l.keys_sorted = c.take<uint64_t>(P);
-    l.vals = c.take<uint32_t>(P);
-    l.vals_sorted = c.take<uint32_t>(P);
-    l.sort_bytes = sort_u64_scratch(P);
-    l.sort_tmp = c.take<char>(l.sort_bytes);
+    sort_layout(c, P, l.sort);
     l.sp = c.take<float4>(P);
     l.leaves = c.take<Box>(nleaves);
     l.subs = c.take<Box>((size_t)nleaves * kSub);
@@ -716,16 +551,18 @@ int dist_cuda2(hidegs_alloc_fn alloc, void* user, int P, const float* points, fl
 
     if (hipMemsetAsync(l.counters, 0, l.counter_bytes, stream) != hipSuccess)
         return fail(HIDEGS_E_HIP, "distCUDA2: memset failed");
-    HIDEGS_LAUNCH("bounds", bounds_kernel, dim3(nbound), dim3(kBlock), 0, stream, points, P, l.partials);
-    HIDEGS_LAUNCH("bounds_finalize", bounds_finalize_kernel, dim3(1), dim3(kBlock), 0, stream, l.partials, nbound, l.params);
-    HIDEGS_LAUNCH("morton", morton_kernel, dim3(nb), dim3(kBlock), 0, stream, points, P, l.params, l.keys, l.vals);
-    int rc = sort_pairs_u64(l.sort_tmp, l.sort_bytes, l.keys, l.keys_sorted, l.vals, l.vals_sorted, P, 0,
-                            3 * kMortonBits, stream);
+    HIDEGS_LAUNCH("bounds", tree_bounds_kernel<KnnTree>, dim3(nbound), dim3(kTreeBlock), 0, stream, points, P, l.partials);
+    HIDEGS_LAUNCH("bounds_finalize", tree_frame_kernel<KnnTree>, dim3(1), dim3(kTreeBlock), 0, stream, l.partials, nbound,
+                  l.params);
+    HIDEGS_LAUNCH("morton", tree_point_keys_kernel<KnnTree>, dim3(nb), dim3(kTreeBlock), 0, stream, points, P, l.params,
+                  l.sort.keys, l.sort.vals);
+    int rc = sort_pairs_u64(l.sort.sort_tmp, l.sort.sort_bytes, l.sort.keys, l.sort.keys_sorted, l.sort.vals,
+                            l.sort.vals_sorted, P, 0, 3 * kMortonBits, stream);
     if (rc) return rc;
-    HIDEGS_LAUNCH("gather", gather_kernel, dim3(nb), dim3(kBlock), 0, stream, points, l.vals_sorted, P, l.sp, nleaves,
+    HIDEGS_LAUNCH("gather", gather_kernel, dim3(nb), dim3(kBlock), 0, stream, points, l.sort.vals_sorted, P, l.sp, nleaves,
                   l.leaves, l.subs);
-    HIDEGS_LAUNCH("super_box", super_box_kernel, dim3(ceil_div(nsuper, kWaves)), dim3(kBlock), 0, stream, l.leaves, nleaves,
-                       nsuper, l.supers);
+    HIDEGS_LAUNCH("super_box", tree_super_kernel<KnnTree>, dim3(ceil_div(nsuper, kTreeWaves)), dim3(kTreeBlock), 0, stream,
+                  l.leaves, nleaves, nsuper, l.supers);
     HIDEGS_LAUNCH("knn_leaf", knn_leaf_kernel, dim3(ceil_div(nleaves, kWaves)), dim3(kBlock), 0, stream, l.sp, P, nleaves,
                        nsuper, l.leaves, l.subs, l.supers, mean_dists, l.hard, l.counters);
     HIDEGS_LAUNCH("knn_hard", knn_hard_kernel, dim3(std::min(2048, ceil_div(nleaves, kWaves))), dim3(kBlock), 0, stream, l.sp,

@@ -57,11 +57,6 @@ struct Out {
     float *mean, *cov, *evals, *evecs;
 };
 
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for a NaN
-}
-
 // The entries of query j < Q: ent[0 .. L).  Nothing at or past capacity is inside it, whatever starts holds.
 __device__ __forceinline__ void list_span(const Lists& ls, uint32_t j, const int32_t*& ent, uint32_t& L)
 {
@@ -160,11 +155,6 @@ __device__ __forceinline__ void lane_total(const Cloud& c, const int32_t* __rest
     }
 }
 
-__device__ __forceinline__ float read_lane(float v, uint32_t lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)lane));
-}
-
 // One wave, the whole list (ent and L wave-uniform, L > 0): lane l sums block 64 r + l in round r, then every
 // lane adds the round's partials in lane order.  Every lane ends with the same totals; cnt is the lane's own.
 template <typename Pass>
@@ -184,7 +174,7 @@ __device__ __forceinline__ void wave_total(const Cloud& c, const int32_t* __rest
         for (uint32_t l = 0; l < lanes; l++) {
 #pragma unroll
             for (int s = 0; s < Pass::N; s++) {
-                const float v = read_lane(part[s], l);
+                const float v = uniform_lane(part[s], (int)l);
                 tot[s] = (b0 == 0 && l == 0) ? v : tot[s] + v;
             }
         }
@@ -327,15 +317,8 @@ __global__ __launch_bounds__(kBlock) void moments_lane_kernel(Cloud c, Lists ls,
         if (active) list_span(ls, j, ent, L);
         const bool is_long = L > kLaneBlocks * kSum;
         if (long_list) {  // the long lists of this wave: one atomic, then every lane its own slot
-            const uint64_t ballot = __ballot(is_long);
-            if (ballot) {
-                const uint32_t lane = lane_id();
-                const int leader = __ffsll((long long)ballot) - 1;
-                uint32_t at = 0;
-                if ((int)lane == leader) at = atomicAdd(long_count, (uint32_t)__popcll(ballot));
-                at = (uint32_t)__builtin_amdgcn_readlane((int)at, leader);
-                if (is_long) long_list[at + __popcll(ballot & ((1ull << lane) - 1))] = j;
-            }
+            const uint32_t at = wave_append(is_long, long_count);
+            if (is_long) long_list[at] = j;
         }
         if (!active || is_long) continue;
         float s[4], m[3], cc[6];

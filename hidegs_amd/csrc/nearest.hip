@@ -1,8 +1,8 @@
 // nearest.hip -- nearest-point index (include/hidegs_nearest.h): built once over a (P,3) cloud, then asked for
 // the nearest point of arbitrary query positions.  Exact: the candidate minimising (bits(d), row index).
 //
-// Build (the structure distCUDA2 searches, knn.hip, kept in a caller-owned buffer; the builders below
-// resemble knn.hip's on purpose -- that file is closed, and folding both onto one header is a later change):
+// Build (the structure distCUDA2 searches, knn.hip, kept in a caller-owned buffer: the constants, the distance,
+// the lower bounds, the keys and the build kernels but the gather are morton_tree.h's, shared with that file):
 //   1. bounding box over the finite rows (grid-stride partials + one finishing workgroup), no host read;
 //   2. 48-bit Morton keys (16 bits per axis), kept below the largest, which the rows with a non-finite
 //      coordinate take alone: they sort strictly last;
@@ -47,28 +47,24 @@
 #include "../../include/hidegs_nearest_within.h"
 #include "../../include/hidegs_nearest_lists.h"
 #include "common.h"
+#include "morton_tree.h"
 
 namespace hidegs {
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;  // 4
-constexpr int kLeaf = 64;               // points per leaf
-constexpr int kFan = 64;                // leaves per super-box
-constexpr int kMortonBits = 16;         // per axis
-constexpr int kBoundBlocks = 1024;
 constexpr int kListCap = 256;           // candidate leaves buffered per wave
 constexpr int kBailout = 256;           // candidate leaves after which a wave hands its queries to phase 2
 constexpr int kSpanBail = 16;           // leaves between a wave's first and last key above which it does so unseeded
 constexpr int kHardGrid = 4096;         // workgroups of phase 2 at most
 constexpr long long kNearestMax = 0x7fffffffLL;
 constexpr uint32_t kInfBits = 0x7f800000u;
-constexpr uint64_t kLastKey = 0xffffffffffffull;  // of a non-candidate row
-static_assert(kLeaf == kWave, "one lane per point of a leaf");
 static_assert(kBailout <= kListCap, "the list holds every leaf of a wave that does not bail");
 
-struct Box {
-    float4 lo, hi;
+// A row with a non-finite coordinate is no candidate: out of every box, sorted strictly last (morton_tree.h).
+struct NearestTree {
+    static constexpr bool kNonFiniteLast = true;
 };
 
 struct Counters {
@@ -76,40 +72,6 @@ struct Counters {
 };
 
 inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for a NaN
-}
-
-__device__ __forceinline__ float sqdist(float4 q, float4 c)
-{
-    const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
-    return fmaf(dz, dz, fmaf(dx, dx, dy * dy));
-}
-
-// Bits of a lower bound of sqdist(q, c) over c in the box: the same monotone expression.
-__device__ __forceinline__ uint32_t box_point_lb(const Box& b, float4 q)
-{
-    const float gx = fmaxf(fmaxf(b.lo.x - q.x, q.x - b.hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(b.lo.y - q.y, q.y - b.hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(b.lo.z - q.z, q.z - b.hi.z), 0.f);
-    return __float_as_uint(fmaf(gz, gz, fmaf(gx, gx, gy * gy)));
-}
-
-// The same over every query in the AABB [qlo, qhi].
-__device__ __forceinline__ uint32_t box_box_lb(const Box& b, float4 qlo, float4 qhi)
-{
-    const float gx = fmaxf(fmaxf(b.lo.x - qhi.x, qlo.x - b.hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(b.lo.y - qhi.y, qlo.y - b.hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(b.lo.z - qhi.z, qlo.z - b.hi.z), 0.f);
-    return __float_as_uint(fmaf(gz, gz, fmaf(gx, gx, gy * gy)));
-}
-
-__device__ __forceinline__ float uniform_lane(float v, int src)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
 
 __device__ __forceinline__ uint64_t pack(float d, float row_bits)
 {
@@ -127,123 +89,25 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
     return ((uint64_t)mh << 32) | ml;
 }
 
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (lane == 0) ? 0ull : (~0ull >> (64 - lane)); }
-
-__device__ __forceinline__ uint64_t spread3(uint32_t v)
+// Bits of morton_tree.h's lower bounds: what the searches compare.
+__device__ __forceinline__ uint32_t point_lb_bits(const Box& b, float4 q) { return __float_as_uint(box_point_lb(b, q)); }
+__device__ __forceinline__ uint32_t box_lb_bits(const Box& b, float4 qlo, float4 qhi)
 {
-    // bit i of v -> bit 3i (v < 2^21)
-    uint64_t x = v & 0x1fffffu;
-    x = (x | (x << 32)) & 0x001f00000000ffffull;
-    x = (x | (x << 16)) & 0x001f0000ff0000ffull;
-    x = (x | (x << 8)) & 0x100f00f00f00f00full;
-    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
+    return __float_as_uint(box_box_lb(b, qlo, qhi));
 }
 
-// Morton key of a position in the frame {lo.xyz, scale.xyz}, clamped into the box (a NaN goes to 0) and kept
-// below kLastKey: the non-candidate rows alone have that key, so they sort strictly last, behind every
-// candidate, and no query's key -- one beyond the box's far corner included -- falls into a leaf that holds
-// only them (find_leaf then seeds from the last leaf with a candidate).  The key orders; it decides no result.
-__device__ __forceinline__ uint64_t morton_key(float x, float y, float z, const float* __restrict__ frame)
+// Key of a query position: morton_tree.h's, kept below kLastKey like every candidate's.  The non-candidate rows
+// alone have that key, so they sort strictly last, behind every candidate, and no query's key -- one beyond the
+// box's far corner included -- falls into a leaf that holds only them (find_leaf then seeds from the last leaf
+// with a candidate).
+__device__ __forceinline__ uint64_t query_key(float x, float y, float z, const float* __restrict__ frame)
 {
-    const float qmax = (float)((1u << kMortonBits) - 1u);
-    const float v[3] = {x, y, z};
-    uint64_t code = 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        float t = (v[a] - frame[a]) * frame[3 + a];
-        t = fminf(fmaxf(t, 0.f), qmax);
-        code |= spread3((uint32_t)t) << a;
-    }
-    return min(code, kLastKey - 1);
+    return min(morton_key(x, y, z, frame), kLastKey - 1);
 }
 
-// ---- build: bounds ------------------------------------------------------------------------------------
-// Workgroup minimum and maximum per axis: thread a < 3 receives axis a's in (l, h).  (Indexing lo[] and hi[]
-// by the thread index instead would make the compiler move both arrays to LDS, 6 KiB a workgroup.)
-__device__ __forceinline__ void block_minmax(float (&lo)[3], float (&hi)[3], float (*s)[6], float& l, float& h)
-{
-    const int wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        lo[a] = wave_min(lo[a]);
-        hi[a] = wave_max(hi[a]);
-    }
-    if (lane_id() == 0)
-        for (int a = 0; a < 3; a++) {
-            s[wave][a] = lo[a];
-            s[wave][3 + a] = hi[a];
-        }
-    __syncthreads();
-    l = FLT_MAX, h = -FLT_MAX;
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        for (int w = 0; w < kWaves; w++) {
-            l = fminf(l, s[w][a]);
-            h = fmaxf(h, s[w][3 + a]);
-        }
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void nearest_bounds_kernel(const float* __restrict__ pts, long long P,
-                                                                float* __restrict__ partials)
-{
-    __shared__ float s[kWaves][6];
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock) {
-        const float v[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-        if (!finite3(v[0], v[1], v[2])) continue;  // no candidate: it widens nothing
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], v[a]);
-            hi[a] = fmaxf(hi[a], v[a]);
-        }
-    }
-    float l, h;
-    block_minmax(lo, hi, s, l, h);
-    if (threadIdx.x < 3) {
-        partials[blockIdx.x * 6 + threadIdx.x] = l;
-        partials[blockIdx.x * 6 + 3 + threadIdx.x] = h;
-    }
-}
-
-// frame = {lo.x, lo.y, lo.z, scale.x, scale.y, scale.z}
-__global__ __launch_bounds__(kBlock) void nearest_frame_kernel(const float* __restrict__ partials, int nparts,
-                                                               float* __restrict__ frame)
-{
-    __shared__ float s[kWaves][6];
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int b = threadIdx.x; b < nparts; b += kBlock)
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], partials[b * 6 + a]);
-            hi[a] = fmaxf(hi[a], partials[b * 6 + 3 + a]);
-        }
-    float l, h;
-    block_minmax(lo, hi, s, l, h);
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        const float ext = h - l;  // negative without a candidate
-        const float q = (float)((1u << kMortonBits) - 1u);
-        frame[a] = l;
-        frame[3 + a] = (ext > 0.f && ext < INFINITY) ? q / ext : 0.f;
-    }
-}
-
-// ---- build: keys, gather, boxes -----------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void nearest_point_keys_kernel(const float* __restrict__ pts, long long P,
-                                                                    const float* __restrict__ frame,
-                                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
-{
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= P) return;
-    const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    keys[i] = finite3(x, y, z) ? morton_key(x, y, z, frame) : kLastKey;
-    vals[i] = (uint32_t)i;
-}
-
-// Sorted point j = row order[j] as {x, y, z, bits(row)}.  Wave w of block b holds leaf 4b + w and writes its
-// box and first key.
+// ---- build: gather ------------------------------------------------------------------------------------
+// Sorted point j = row order[j] as {x, y, z, bits(row)}; a non-candidate row is stored as three NaNs.  Wave w of
+// block b holds leaf 4b + w and writes its box and first key.
 __global__ __launch_bounds__(kBlock) void nearest_gather_kernel(const float* __restrict__ pts, const uint32_t* __restrict__ order,
                                                                 const uint64_t* __restrict__ keys_sorted, long long P,
                                                                 float4* __restrict__ sp, long long nleaves,
@@ -273,20 +137,6 @@ __global__ __launch_bounds__(kBlock) void nearest_gather_kernel(const float* __r
     }
 }
 
-__global__ __launch_bounds__(kBlock) void nearest_super_kernel(const Box* __restrict__ leaves, long long nleaves, int nsuper,
-                                                               Box* __restrict__ supers)
-{
-    const int S = blockIdx.x * kWaves + threadIdx.x / kWave;
-    if (S >= nsuper) return;
-    const long long l = (long long)S * kFan + lane_id();
-    const Box b = l < nleaves ? leaves[l]
-                              : Box{make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.f), make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.f)};
-    Box r;
-    r.lo = make_float4(wave_min(b.lo.x), wave_min(b.lo.y), wave_min(b.lo.z), 0.f);
-    r.hi = make_float4(wave_max(b.hi.x), wave_max(b.hi.y), wave_max(b.hi.z), 0.f);
-    if (lane_id() == 0) supers[S] = r;
-}
-
 // ---- query --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void nearest_query_keys_kernel(const float* __restrict__ queries, long long Q,
                                                                     const float* __restrict__ frame,
@@ -294,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void nearest_query_keys_kernel(const float*
 {
     const long long j = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (j >= Q) return;
-    keys[j] = morton_key(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], frame);
+    keys[j] = query_key(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2], frame);
     vals[j] = (uint32_t)j;
 }
 
@@ -337,15 +187,11 @@ __device__ __forceinline__ long long find_leaf(const uint64_t* __restrict__ leaf
 
 // Appends the sorted position `s` of every lane with `flag` to the hard list (phase 2's input): one atomic per
 // wave.  A query is appended once at most, so the list holds at most Q entries.
-__device__ __forceinline__ void push_hard(bool flag, long long s, int lane, uint32_t* __restrict__ hard,
+__device__ __forceinline__ void push_hard(bool flag, long long s, uint32_t* __restrict__ hard,
                                           Counters* __restrict__ counters)
 {
-    const uint64_t m = __ballot(flag);
-    if (!m) return;
-    uint32_t at = 0;
-    if (lane == 0) at = atomicAdd(&counters->hard, (uint32_t)__popcll(m));
-    at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
-    if (flag) hard[at + __popcll(m & lanes_below(lane))] = (uint32_t)s;
+    const uint32_t at = wave_append(flag, &counters->hard);
+    if (flag) hard[at] = (uint32_t)s;
 }
 
 // The point held by lane c of `pt`, broadcast to every lane.
@@ -410,7 +256,7 @@ __device__ __forceinline__ void lane_walk(Searcher& sr, const IndexView& ix, con
         const long long lf = find_leaf(ix.leaf_keys, nleaves, qkeys[base], lane);
         const long long ll = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave - 1, Q - 1)], lane);
         if (ll - lf > kSpanBail) {
-            push_hard(active, s, lane, hard, counters);
+            push_hard(active, s, hard, counters);
             return;
         }
     }
@@ -446,7 +292,7 @@ __device__ __forceinline__ void lane_walk(Searcher& sr, const IndexView& ix, con
     for (int s0 = 0; s0 < nsuper && !bail; s0 += kWave) {  // one super-box per lane
         const int sidx = s0 + lane;
         bool pass = false;
-        if (sidx < nsuper) pass = box_box_lb(ix.supers[sidx], qlo, qhi) <= ub;
+        if (sidx < nsuper) pass = box_lb_bits(ix.supers[sidx], qlo, qhi) <= ub;
         uint64_t smask = __ballot(pass);
         while (smask) {
             const int S = s0 + __builtin_ctzll(smask);
@@ -454,7 +300,7 @@ __device__ __forceinline__ void lane_walk(Searcher& sr, const IndexView& ix, con
             const long long l = (long long)S * kFan + lane;
             bool lpass = false;
             if (l < nleaves && (l < Ls - 1 || l > Ls + 1))  // those three were the seed
-                lpass = box_box_lb(ix.leaves[l], qlo, qhi) <= ub;
+                lpass = box_lb_bits(ix.leaves[l], qlo, qhi) <= ub;
             const uint64_t lm = __ballot(lpass);
             const int cnt = __popcll(lm);
             if (cnt == 0) continue;
@@ -471,7 +317,7 @@ __device__ __forceinline__ void lane_walk(Searcher& sr, const IndexView& ix, con
         // The wave's queries are spread too far for one coarse filter (queries far outside the cloud, on both
         // sides of a Morton jump, or with a large radius): phase 2 searches each again from nothing, with its
         // own seed and bound.
-        push_hard(active, s, lane, hard, counters);
+        push_hard(active, s, hard, counters);
         return;
     }
 
@@ -480,11 +326,11 @@ __device__ __forceinline__ void lane_walk(Searcher& sr, const IndexView& ix, con
         const Box lb = ix.leaves[C];  // wave-uniform address
         // fine filter: some live lane's own bound reaches the leaf
         const uint32_t bound = sr.bound(active, live);
-        if (!__ballot(live && box_point_lb(lb, q) <= bound)) continue;
+        if (!__ballot(live && point_lb_bits(lb, q) <= bound)) continue;
         const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
         const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
         // a point is evaluated if it is a candidate within the largest live bound of the query AABB
-        uint64_t pm = __ballot(lane < nc && pt.x == pt.x && box_point_lb(Box{qlo, qhi}, pt) <= ub);
+        uint64_t pm = __ballot(lane < nc && pt.x == pt.x && point_lb_bits(Box{qlo, qhi}, pt) <= ub);
         while (pm) {
             const int c = __builtin_ctzll(pm);
             pm &= pm - 1;
@@ -555,14 +401,14 @@ __global__ __launch_bounds__(kBlock) void nearest_hard_kernel(IndexView ix, cons
         for (int s0 = 0; s0 < ix.nsuper; s0 += kWave) {  // one super-box per lane
             const int sidx = s0 + lane;
             bool pass = false;
-            if (sidx < ix.nsuper) pass = box_point_lb(ix.supers[sidx], q) <= bound_bits(best);
+            if (sidx < ix.nsuper) pass = point_lb_bits(ix.supers[sidx], q) <= bound_bits(best);
             uint64_t smask = __ballot(pass);
             while (smask) {
                 const int S = s0 + __builtin_ctzll(smask);
                 smask &= smask - 1;
                 const long long l = (long long)S * kFan + lane;
                 bool lpass = false;
-                if (l < nleaves && (l < L - 1 || l > L + 1)) lpass = box_point_lb(ix.leaves[l], q) <= bound_bits(best);
+                if (l < nleaves && (l < L - 1 || l > L + 1)) lpass = point_lb_bits(ix.leaves[l], q) <= bound_bits(best);
                 uint64_t lmask = __ballot(lpass);
                 if (!lmask) continue;
                 while (lmask) {
@@ -606,26 +452,8 @@ IndexLayout index_layout(void* base, long long P)
     return l;
 }
 
-// Both calls sort n (key, row) pairs.
-struct SortLayout {
-    uint64_t *keys, *keys_sorted;
-    uint32_t *vals, *vals_sorted;
-    void* sort_tmp;
-    size_t sort_bytes;
-};
-
-void sort_layout(Carver& c, long long n, SortLayout& l)
-{
-    l.keys = c.take<uint64_t>(n);
-    l.keys_sorted = c.take<uint64_t>(n);
-    l.vals = c.take<uint32_t>(n);
-    l.vals_sorted = c.take<uint32_t>(n);
-    l.sort_bytes = sort_u64_scratch(n);
-    l.sort_tmp = c.take<char>(l.sort_bytes);
-}
-
 struct BuildLayout {
-    SortLayout sort;
+    SortLayout sort;  // both calls sort n (key, row) pairs
     float* partials;
     size_t total;
 };
@@ -657,8 +485,6 @@ QueryLayout query_layout(void* base, long long Q)
     l.total = c.used;
     return l;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 bool overlap(const void* a, size_t na, const void* b, size_t nb)
 {
@@ -790,16 +616,16 @@ extern "C" int hidegs_nearest_build(void* index, size_t index_bytes, void* scrat
     const BuildLayout b = build_layout(scratch, P);
     const int nb = (int)ceil_div(P, kBlock);
     const int nbound = std::min(kBoundBlocks, nb);
-    HIDEGS_LAUNCH("nearest_bounds", nearest_bounds_kernel, dim3(nbound), dim3(kBlock), 0, s, points, P, b.partials);
-    HIDEGS_LAUNCH("nearest_frame", nearest_frame_kernel, dim3(1), dim3(kBlock), 0, s, b.partials, nbound, ix.frame);
-    HIDEGS_LAUNCH("nearest_point_keys", nearest_point_keys_kernel, dim3(nb), dim3(kBlock), 0, s, points, P, ix.frame,
+    HIDEGS_LAUNCH("nearest_bounds", tree_bounds_kernel<NearestTree>, dim3(nbound), dim3(kTreeBlock), 0, s, points, P, b.partials);
+    HIDEGS_LAUNCH("nearest_frame", tree_frame_kernel<NearestTree>, dim3(1), dim3(kTreeBlock), 0, s, b.partials, nbound, ix.frame);
+    HIDEGS_LAUNCH("nearest_point_keys", tree_point_keys_kernel<NearestTree>, dim3(nb), dim3(kTreeBlock), 0, s, points, P, ix.frame,
                   b.sort.keys, b.sort.vals);
     if (int rc = sort_pairs_u64(b.sort.sort_tmp, b.sort.sort_bytes, b.sort.keys, b.sort.keys_sorted, b.sort.vals,
                                 b.sort.vals_sorted, P, 0, 3 * kMortonBits, s))
         return rc;
     HIDEGS_LAUNCH("nearest_gather", nearest_gather_kernel, dim3(nb), dim3(kBlock), 0, s, points, b.sort.vals_sorted,
                   b.sort.keys_sorted, P, ix.sp, ix.nleaves, ix.leaves, ix.leaf_keys);
-    HIDEGS_LAUNCH("nearest_super", nearest_super_kernel, dim3((unsigned)ceil_div(ix.nsuper, kWaves)), dim3(kBlock), 0, s,
+    HIDEGS_LAUNCH("nearest_super", tree_super_kernel<NearestTree>, dim3((unsigned)ceil_div(ix.nsuper, kTreeWaves)), dim3(kTreeBlock), 0, s,
                   ix.leaves, ix.nleaves, ix.nsuper, ix.supers);
     return check_launch("nearest_build", s, 0);
 }

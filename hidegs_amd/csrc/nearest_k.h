@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void nearest_route_kernel(const float* __re
         active = sr.load(j) && finite3(queries[3 * j], queries[3 * j + 1], queries[3 * j + 2]);
         if (!active) sr.store_none(j);
     }
-    push_hard(active, s, lane_id(), hard, counters);
+    push_hard(active, s, hard, counters);
 }
 
 // One wave per hard query, for both list queries.  Lane i holds the i-th best (~0: none yet); kth is lane
@@ -213,14 +213,14 @@ __device__ __forceinline__ void hard_list_walk(const IndexView& ix, const float*
         for (int s0 = 0; s0 < ix.nsuper && open(); s0 += kWave) {  // one super-box per lane
             const int sidx = s0 + lane;
             bool pass = false;
-            if (sidx < ix.nsuper) pass = box_point_lb(ix.supers[sidx], q) <= bnd;
+            if (sidx < ix.nsuper) pass = point_lb_bits(ix.supers[sidx], q) <= bnd;
             uint64_t smask = __ballot(pass);
             while (smask && open()) {
                 const int S = s0 + __builtin_ctzll(smask);
                 smask &= smask - 1;
                 const long long l = (long long)S * kFan + lane;
                 uint32_t llb = 0xffffffffu;  // above every bound: no leaf, or one of the seed
-                if (l < nleaves && (l < L - 1 || l > L + 1)) llb = box_point_lb(ix.leaves[l], q);
+                if (l < nleaves && (l < L - 1 || l > L + 1)) llb = point_lb_bits(ix.leaves[l], q);
                 uint64_t lmask = __ballot(llb <= bnd);
                 while (lmask && open()) {
                     const int b = __builtin_ctzll(lmask);

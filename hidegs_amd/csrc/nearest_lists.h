@@ -85,14 +85,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
         for (int s0 = 0; s0 < nsuper && base < end; s0 += kWave) {  // one super-box per lane
             const int sidx = s0 + lane;
             bool pass = false;
-            if (sidx < nsuper) pass = box_point_lb(ix.supers[sidx], q) <= rb;
+            if (sidx < nsuper) pass = point_lb_bits(ix.supers[sidx], q) <= rb;
             uint64_t smask = __ballot(pass);
             while (smask && base < end) {
                 const int S = s0 + __builtin_ctzll(smask);
                 smask &= smask - 1;
                 const long long l = (long long)S * kFan + lane;  // one leaf per lane
                 bool lpass = false;
-                if (l < nleaves) lpass = box_point_lb(ix.leaves[l], q) <= rb;
+                if (l < nleaves) lpass = point_lb_bits(ix.leaves[l], q) <= rb;
                 uint64_t lmask = __ballot(lpass);
                 while (lmask && base < end) {
                     const long long c = ((long long)S * kFan + __builtin_ctzll(lmask)) * kLeaf + lane;  // one point per lane

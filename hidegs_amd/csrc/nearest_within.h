@@ -166,7 +166,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
         const long long lf = find_leaf(ix.leaf_keys, nleaves, qkeys[base], lane);
         const long long ll = find_leaf(ix.leaf_keys, nleaves, qkeys[min(base + kWave - 1, Q - 1)], lane);
         if (ll - lf > kSpanBail) {
-            push_hard(active, s, lane, hard, counters);
+            push_hard(active, s, hard, counters);
             return;
         }
     }
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
     for (int s0 = 0; s0 < nsuper && !bail; s0 += kWave) {  // one super-box per lane
         const int sidx = s0 + lane;
         bool pass = false;
-        if (sidx < nsuper) pass = box_box_lb(ix.supers[sidx], qlo, qhi) <= ub;
+        if (sidx < nsuper) pass = box_lb_bits(ix.supers[sidx], qlo, qhi) <= ub;
         uint64_t smask = __ballot(pass);
         while (smask) {
             const int S = s0 + __builtin_ctzll(smask);
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
             const long long l = (long long)S * kFan + lane;
             bool lpass = false;
             if (l < nleaves && (l < Ls - 1 || l > Ls + 1))  // those three were the seed
-                lpass = box_box_lb(ix.leaves[l], qlo, qhi) <= ub;
+                lpass = box_lb_bits(ix.leaves[l], qlo, qhi) <= ub;
             const uint64_t lm = __ballot(lpass);
             const int cnt = __popcll(lm);
             if (cnt == 0) continue;
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
         }
     }
     if (bail) {
-        push_hard(active, s, lane, hard, counters);  // the hard kernel starts each of them again from nothing
+        push_hard(active, s, hard, counters);  // the hard kernel starts each of them again from nothing
         return;
     }
 
@@ -230,11 +230,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
         const Box lb = ix.leaves[C];  // wave-uniform address
         // fine filter: some live lane's own bound reaches the leaf
         const uint32_t bound = bound_within<K>(active, count, max_count, rb, list, live);
-        if (!__ballot(live && box_point_lb(lb, q) <= bound)) continue;
+        if (!__ballot(live && point_lb_bits(lb, q) <= bound)) continue;
         const float4 pt = ix.sp[min(C * kLeaf + lane, P - 1)];
         const int nc = (int)min((long long)kLeaf, P - C * kLeaf);
         // a point is evaluated if it is a candidate within the largest live bound of the query AABB
-        uint64_t pm = __ballot(lane < nc && pt.x == pt.x && box_point_lb(Box{qlo, qhi}, pt) <= ub);
+        uint64_t pm = __ballot(lane < nc && pt.x == pt.x && point_lb_bits(Box{qlo, qhi}, pt) <= ub);
         while (pm) {
             const int c = __builtin_ctzll(pm);
             pm &= pm - 1;

@@ -210,7 +210,6 @@ __global__ __launch_bounds__(kBlock) void move_rows_kernel(const RowBatch batch,
         move_units<kScatter, uint32_t>(F, u0, indices);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int move_rows(bool scatter, const hidegs_row_field* fields, int nfields, const uint32_t* indices, long long k,
               hipStream_t stream)

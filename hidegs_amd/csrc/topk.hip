@@ -302,7 +302,6 @@ size_t topk_scratch(long long n)
     return align_up((size_t)kPasses * kRadix * sizeof(uint32_t)) + align_up((size_t)kPasses * sizeof(State)) +
            align_up((size_t)topk_tiles(n) * sizeof(uint32_t));
 }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace hidegs

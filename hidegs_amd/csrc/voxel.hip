@@ -58,11 +58,6 @@ constexpr uint32_t kSmallMax = 32;          // rows of a small group
 constexpr uint32_t kChunk = 512;            // rows of a chunk, and of the largest medium group
 constexpr int kGridCap = 8192;              // workgroups of a launch over the groups: 32 per CU, the rest by stride
 
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for a NaN
-}
-
 __device__ __forceinline__ bool eligible(const float* __restrict__ pts, const uint8_t* __restrict__ among, long long i,
                                          float (&v)[3])
 {

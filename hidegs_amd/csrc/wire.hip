@@ -141,7 +141,6 @@ __global__ __launch_bounds__(kBlock) void mask_union_count_kernel(const uint8_t*
     count[i] = (float)c;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 unsigned grid_for(long long n)
 {

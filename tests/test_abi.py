@@ -174,6 +174,24 @@ def test_scratch_sizes_grow_with_n(built_lib):
     assert built_lib.hidegs_knn_scratch_bytes(2_000_000) > 50 * 2_000_000
 
 
+def test_tree_layout_sizes_are_pinned(built_lib):
+    """distCUDA2's scratch and the nearest index's three buffers carve the same arrays in the same order as before
+    morton_tree.h held their shared sort layout: every size below is a literal returned by a build of the commit
+    before that header existed (957c5ca), not a formula restated from the code under test.  knn_stats.h finds its
+    block by distCUDA2's carving order, and callers size their buffers by these functions."""
+    sizes = (1, 63, 64, 65, 4096, 4097, 262145, 2**31 - 1)
+    knn = (336896, 338944, 338944, 340992, 585472, 589056, 16473600, 132193487616)
+    index = (1280, 2048, 2048, 2304, 68608, 69376, 4361472, 35718693120)
+    build = (335104, 336384, 336384, 337920, 492544, 495104, 10571520, 83858327808)
+    query = (311040, 312320, 312320, 314112, 484608, 487424, 11596032, 92448238080)  # by Q, for every P
+    for i, n in enumerate(sizes):
+        assert built_lib.hidegs_knn_scratch_bytes(n) == knn[i], n
+        assert built_lib.hidegs_nearest_index_bytes(n) == index[i], n
+        assert built_lib.hidegs_nearest_build_scratch_bytes(n) == build[i], n
+        for P in sizes:
+            assert built_lib.hidegs_nearest_query_scratch_bytes(P, n) == query[i], (P, n)
+
+
 def test_alloc_callback_invoked_once_and_failure_surfaces(built_lib):
     """distCUDA2 asks its scratch callback exactly once for hidegs_knn_scratch_bytes(P); a callback
     that fails (here: resize_ of a host tensor past a hard limit raises) returns NULL, the library

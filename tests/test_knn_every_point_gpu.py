@@ -28,8 +28,8 @@ from test_knn_gpu import assert_bits_equal, knn
 
 pytestmark = pytest.mark.gpu
 
-# knn.hip's constants, restated: if one of them changes, the thresholds asserted below move and these
-# tests fail instead of silently reaching nothing.
+# knn.hip's constants (kLeaf and kFan: morton_tree.h's), restated: if one of them changes, the thresholds
+# asserted below move and these tests fail instead of silently reaching nothing.
 K_LEAF, K_FAN, K_WAVE, K_SUPER_BATCH = 64, 64, 64, 2
 PHASE1_BATCH = K_WAVE * K_SUPER_BATCH  # super-boxes per iteration of phase 1's s0 loop
 PHASE2_BATCH = K_WAVE
@@ -43,10 +43,10 @@ def nsuper(P):
 def test_restated_constants_match_knn_hip():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hidegs_amd", "csrc", "knn.hip")).read()
-    common = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hidegs_amd", "csrc", "common.h")).read()
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hidegs_amd", "csrc")
+    src, tree, common = (open(os.path.join(csrc, name)).read() for name in ("knn.hip", "morton_tree.h", "common.h"))
     found = {name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
-             for name, text in (("kLeaf", src), ("kFan", src), ("kSuperBatch", src), ("kWave", common))}
+             for name, text in (("kLeaf", tree), ("kFan", tree), ("kSuperBatch", src), ("kWave", common))}
     assert found == {"kLeaf": K_LEAF, "kFan": K_FAN, "kSuperBatch": K_SUPER_BATCH, "kWave": K_WAVE}
     assert "s0 += kWave * kSuperBatch" in src and "s0 += kWave)" in src
 

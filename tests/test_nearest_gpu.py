@@ -40,9 +40,10 @@ def test_restated_constants_match_nearest_hip():
     import re
     here = os.path.dirname(os.path.abspath(__file__))
     src = open(os.path.join(here, "..", "hidegs_amd", "csrc", "nearest.hip")).read()
+    tree = open(os.path.join(here, "..", "hidegs_amd", "csrc", "morton_tree.h")).read()  # the leaf and the fan are shared
     common = open(os.path.join(here, "..", "hidegs_amd", "csrc", "common.h")).read()
     found = {name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
-             for name, text in (("kLeaf", src), ("kFan", src), ("kBailout", src), ("kSpanBail", src),
+             for name, text in (("kLeaf", tree), ("kFan", tree), ("kBailout", src), ("kSpanBail", src),
                                 ("kWave", common))}
     assert found == {"kLeaf": K_LEAF, "kFan": K_FAN, "kBailout": K_BAILOUT, "kSpanBail": K_SPAN_BAIL, "kWave": K_WAVE}
     assert src.count("s0 += kWave)") == 2  # phase 1's walk (lane_walk, of all three queries) and phase 2's

@@ -11,18 +11,23 @@
 // block_exclusive_scan and writes the positions through LDS, so the global stores are contiguous.
 // No workgroup waits on another.
 //
-// Gather / scatter: one launch moves every field of a batch of up to kMaxFields.  Consecutive lanes
-// take consecutive floats (or 16-byte quads, where width, bases and therefore every row start allow)
-// of the packed side, which is thus fully coalesced; the row side is contiguous inside a row and, for
-// ascending indices, ascending across rows.  A thread owns kUnroll units a workgroup-stride apart and
-// steps (packed row, column) from one to the next with host-computed increments: one division per
-// thread, not per element.
+// Gather / scatter and resize share the walk over the units of a dense side and the batching of fields.
+// One launch serves a Batch of up to kMaxFields field descriptors (place_field gives each its range of
+// workgroups).  Consecutive lanes take consecutive floats (or 16-byte quads, where width, bases and
+// therefore every row start allow) of the dense side, which is thus fully coalesced.  A thread owns
+// kUnroll units a workgroup-stride apart: first_unit finds the (row, column) of its first with one
+// division per thread, not per element, and next_unit steps to the next with the increments make_walk
+// computed on the host (Walk, the tail of both descriptors).
 //
-// Resize (include/hidegs_resize.h): the row surgery of densification -- prune by a keep list, append new
-// rows -- on every per-Gaussian tensor in one launch per kMaxFields.  The same unit stepping over the dense
-// destination, which is written from three sources: kept rows gathered, appended rows copied, or zeros.
-// With include/hidegs_clone.h a fourth: appended rows gathered from the source by a second index list, the
-// clone and the split of densification (resize_rows_cloned_kernel).
+// Gather / scatter (move_rows, move_rows_kernel<kScatter>, move_units): the dense side is the packed one;
+// the row side is contiguous inside a row and, for ascending indices, ascending across rows.
+//
+// Resize (include/hidegs_resize.h, include/hidegs_clone.h): the row surgery of densification -- prune by a
+// keep list, append new rows -- on every per-Gaussian tensor.  The dense side is the destination, written
+// from four sources (resize_units): kept rows gathered, appended rows copied, zeros, or appended rows gathered
+// from the source by a second index list, the clone and the split of densification.  One host function,
+// resize_rows, serves both entry points, and one kernel template both launches: resize_kernel<true> where
+// the batch has a cloned field, resize_kernel<false>, without that branch, where it has none.
 #include <stdint.h>
 
 #include <string>
@@ -114,29 +119,67 @@ __global__ __launch_bounds__(kBlock) void select_write_kernel(const uint8_t* __r
 int select_tiles(long long n) { return (int)((n + kSelectTile - 1) / kSelectTile); }
 size_t select_scratch(long long n) { return align_up((size_t)select_tiles(n) * sizeof(uint32_t)); }
 
-// ============================== gather / scatter ===============================
+// ============================== fields, batches and the unit walk ==============
 constexpr int kMaxFields = 8;  // fields per launch
 constexpr int kUnroll = 8;     // units per thread, all in flight
 constexpr int kUnitsPerBlock = kBlock * kUnroll;
+
+// How a thread steps through the units of a dense side of rows `width` floats wide (the packed side of a
+// move, the dst of a resize): the last members of both field descriptors.
+struct Walk {
+    uint32_t width;
+    uint32_t unit;     // floats per access: 4 (16-byte accesses on every side) or 1
+    uint32_t step_j;   // (kBlock * unit) / width: dense rows between a thread's consecutive units
+    uint32_t step_c;   // (kBlock * unit) % width: columns
+    double inv_w;
+};
+
+Walk make_walk(int width, uint32_t unit)
+{
+    Walk w;
+    w.width = (uint32_t)width;
+    w.unit = unit;
+    w.step_j = (uint32_t)(kBlock * unit) / w.width;
+    w.step_c = (uint32_t)(kBlock * unit) % w.width;
+    w.inv_w = 1.0 / (double)width;
+    return w;
+}
 
 struct RowField {
     uint32_t* rows;
     uint32_t* packed;
     long long n_rows;
     long long units;   // k * width / unit
-    uint32_t width;
-    uint32_t unit;     // floats per access: 4 (16-byte accesses on both sides) or 1
-    uint32_t step_j;   // (kBlock * unit) / width: packed rows between a thread's consecutive units
-    uint32_t step_c;   // (kBlock * unit) % width: columns
-    double inv_w;
+    Walk w;
 };
 
-// Workgroups [first[f], first[f + 1]) own field f.
-struct RowBatch {
-    int count;
-    int first[kMaxFields + 1];
-    RowField f[kMaxFields];
+// The fields of one launch: workgroups [first[f], first[f + 1]) own field f.
+template <typename Field>
+struct Batch {
+    int count = 0;
+    int first[kMaxFields + 1] = {0};
+    Field f[kMaxFields];
 };
+
+// Appends F to the batch, after the workgroups of the fields before it.
+template <typename Field>
+int place_field(Batch<Field>& batch, const Field& F, const std::string& who)
+{
+    const long long blocks = batch.first[batch.count] + (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
+    if (blocks > 0x7fffffffLL) return fail(HIDEGS_E_ARG, who + ": fields too large for one launch");
+    batch.f[batch.count++] = F;
+    batch.first[batch.count] = (int)blocks;
+    return 0;
+}
+
+// The checks of one entry of a field list that every entry point makes.
+template <typename Field>
+int check_shape(const std::string& who, int i, const Field& a)
+{
+    if (a.width < 1) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": width < 1");
+    if (a.n_rows < 0) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": negative n_rows");
+    return 0;
+}
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -149,31 +192,50 @@ __device__ __forceinline__ long long row_of(long long e, uint32_t w, double inv_
     return r;
 }
 
+// Where a unit starts on the dense side: row j, column c.
+struct UnitAt {
+    long long j;
+    uint32_t c;
+};
+
+// This thread's first unit in the workgroup whose first unit is u0.
+template <uint32_t kUnit>
+__device__ __forceinline__ UnitAt first_unit(const Walk& w, long long u0)
+{
+    const long long e0 = u0 * kUnit;  // the workgroup's first dense element
+    const long long j0 = row_of(e0, w.width, w.inv_w);
+    const uint32_t r = (uint32_t)(e0 - j0 * (long long)w.width) + threadIdx.x * kUnit;  // < width + 1024
+    const uint32_t q = r / w.width;
+    return {j0 + q, r - q * w.width};
+}
+
+// From one of a thread's units to its next, kBlock units on.
+__device__ __forceinline__ void next_unit(const Walk& w, UnitAt& p)
+{
+    p.c += w.step_c;
+    p.j += w.step_j;
+    if (p.c >= w.width) {
+        p.c -= w.width;
+        p.j++;
+    }
+}
+
+// ============================== gather / scatter ===============================
 template <bool kScatter, typename V>
 __device__ __forceinline__ void move_units(const RowField& F, long long u0, const uint32_t* __restrict__ indices)
 {
     constexpr uint32_t kUnit = sizeof(V) / sizeof(uint32_t);
-    const long long e0 = u0 * kUnit;  // the workgroup's first packed element
-    const long long j0 = row_of(e0, F.width, F.inv_w);
-    const uint32_t r = (uint32_t)(e0 - j0 * (long long)F.width) + threadIdx.x * kUnit;  // < width + 1024
-    const uint32_t q = r / F.width;
-    long long j = j0 + q;            // packed row and column of this thread's first unit
-    uint32_t c = r - q * F.width;
-    size_t at[kUnroll];              // element offset on the row side
+    UnitAt here = first_unit<kUnit>(F.w, u0);  // on the packed side
+    size_t at[kUnroll];                        // element offset on the row side
     bool ok[kUnroll];
 #pragma unroll
     for (int i = 0; i < kUnroll; i++) {  // every index load issued before any is used
         const long long u = u0 + i * kBlock + threadIdx.x;
-        ok[i] = u < F.units;         // then j < k
-        const uint32_t idx = indices[ok[i] ? j : 0];  // (entry 0 exists: k >= 1)
+        ok[i] = u < F.units;         // then here.j < k
+        const uint32_t idx = indices[ok[i] ? here.j : 0];  // (entry 0 exists: k >= 1)
         ok[i] = ok[i] && (long long)idx < F.n_rows;  // an index past the rows is never dereferenced
-        at[i] = (size_t)idx * F.width + c;
-        c += F.step_c;
-        j += F.step_j;
-        if (c >= F.width) {
-            c -= F.width;
-            j++;
-        }
+        at[i] = (size_t)idx * F.w.width + here.c;
+        next_unit(F.w, here);
     }
     V v[kUnroll];
     const V* src = reinterpret_cast<const V*>(kScatter ? F.packed : F.rows);
@@ -191,7 +253,8 @@ __device__ __forceinline__ void move_units(const RowField& F, long long u0, cons
 }
 
 template <bool kScatter>
-__global__ __launch_bounds__(kBlock) void move_rows_kernel(const RowBatch batch, const uint32_t* __restrict__ indices)
+__global__ __launch_bounds__(kBlock) void move_rows_kernel(const Batch<RowField> batch,
+                                                           const uint32_t* __restrict__ indices)
 {
     // workgroup-uniform selects over constant indices: the descriptors stay in scalar registers
     RowField F = batch.f[0];
@@ -204,12 +267,11 @@ __global__ __launch_bounds__(kBlock) void move_rows_kernel(const RowBatch batch,
         }
     }
     const long long u0 = (long long)((int)blockIdx.x - first) * kUnitsPerBlock;
-    if (F.unit == 4)
+    if (F.w.unit == 4)
         move_units<kScatter, u32x4>(F, u0, indices);
     else
         move_units<kScatter, uint32_t>(F, u0, indices);
 }
-
 
 int move_rows(bool scatter, const hidegs_row_field* fields, int nfields, const uint32_t* indices, long long k,
               hipStream_t stream)
@@ -219,19 +281,15 @@ int move_rows(bool scatter, const hidegs_row_field* fields, int nfields, const u
     if (nfields < 0) return fail(HIDEGS_E_ARG, who + ": negative field count");
     if (k < 0 || k > kSelectMax) return fail(HIDEGS_E_ARG, who + ": k must be in [0, 2^31)");
     if (nfields > 0 && !fields) return fail(HIDEGS_E_ARG, who + ": NULL field list");
-    for (int i = 0; i < nfields; i++) {
-        if (fields[i].width < 1) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": width < 1");
-        if (fields[i].n_rows < 0) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": negative n_rows");
-    }
+    for (int i = 0; i < nfields; i++)
+        if (int rc = check_shape(who, i, fields[i])) return rc;
     if (k == 0 || nfields == 0) return 0;
     if (!indices) return fail(HIDEGS_E_ARG, who + ": NULL indices");
     for (int i = 0; i < nfields; i++)
         if (!fields[i].packed || (fields[i].n_rows > 0 && !fields[i].rows))
             return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": NULL pointer");
     for (int i0 = 0; i0 < nfields; i0 += kMaxFields) {  // kMaxFields per launch
-        RowBatch batch;
-        batch.count = 0;
-        long long blocks = 0;
+        Batch<RowField> batch;
         for (int i = i0; i < nfields && i < i0 + kMaxFields; i++) {
             const hidegs_row_field& a = fields[i];
             if (a.n_rows == 0) continue;  // every index is past the rows
@@ -239,26 +297,17 @@ int move_rows(bool scatter, const hidegs_row_field* fields, int nfields, const u
             F.rows = reinterpret_cast<uint32_t*>(a.rows);
             F.packed = reinterpret_cast<uint32_t*>(a.packed);
             F.n_rows = a.n_rows;
-            F.width = (uint32_t)a.width;
             // width a multiple of 4 and both bases on 16 bytes: every row start and every quad is aligned
-            F.unit = (a.width % 4 == 0 && aligned16(a.rows) && aligned16(a.packed)) ? 4u : 1u;
-            F.units = k * (long long)a.width / F.unit;
-            F.step_j = (uint32_t)(kBlock * F.unit) / F.width;
-            F.step_c = (uint32_t)(kBlock * F.unit) % F.width;
-            F.inv_w = 1.0 / (double)a.width;
-            batch.first[batch.count] = (int)blocks;
-            batch.f[batch.count++] = F;
-            blocks += (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
-            if (blocks > 0x7fffffffLL) return fail(HIDEGS_E_ARG, who + ": fields too large for one launch");
+            F.w = make_walk(a.width, (a.width % 4 == 0 && aligned16(a.rows) && aligned16(a.packed)) ? 4u : 1u);
+            F.units = k * (long long)a.width / F.w.unit;
+            if (int rc = place_field(batch, F, who)) return rc;
         }
         if (batch.count == 0) continue;
-        batch.first[batch.count] = (int)blocks;
+        const dim3 grid((unsigned)batch.first[batch.count]);
         if (scatter)
-            HIDEGS_LAUNCH("scatter_rows", move_rows_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch,
-                          indices);
+            HIDEGS_LAUNCH("scatter_rows", move_rows_kernel<true>, grid, dim3(kBlock), 0, stream, batch, indices);
         else
-            HIDEGS_LAUNCH("gather_rows", move_rows_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch,
-                          indices);
+            HIDEGS_LAUNCH("gather_rows", move_rows_kernel<false>, grid, dim3(kBlock), 0, stream, batch, indices);
     }
     return check_launch(name, stream, 0);
 }
@@ -273,18 +322,7 @@ struct ResizeField {
     long long n_rows;
     long long kept;    // k * width / unit: the units gathered from src
     long long units;   // (k + n_append) * width / unit
-    uint32_t width;
-    uint32_t unit;     // floats per access: 4 (16-byte accesses on all three sides) or 1
-    uint32_t step_j;   // as RowField's
-    uint32_t step_c;
-    double inv_w;
-};
-
-// Workgroups [first[f], first[f + 1]) own field f.
-struct ResizeBatch {
-    int count;
-    int first[kMaxFields + 1];
-    ResizeField f[kMaxFields];
+    Walk w;
 };
 
 // Consecutive lanes take consecutive units of dst.  A unit below F.kept is gathered (dst row j from src row
@@ -294,40 +332,30 @@ struct ResizeBatch {
 // kClone (include/hidegs_clone.h): the field's appended rows are rows of src too, dst row k + i from src row
 // from[i].  Every unit of dst is then a gathered one; only the index array and the entry differ on the two
 // sides of unit F.kept, so the pointer is selected and one load is issued, as for the data.
-template <typename V, bool kKeep, bool kClone = false>
+template <typename V, bool kKeep, bool kClone>
 __device__ __forceinline__ void resize_units(const ResizeField& F, long long u0, const uint32_t* __restrict__ keep,
-                                             const uint32_t* __restrict__ from_list = nullptr, long long k = 0)
+                                             const uint32_t* __restrict__ from_list, long long k)
 {
     constexpr uint32_t kUnit = sizeof(V) / sizeof(uint32_t);
-    const long long e0 = u0 * kUnit;  // the workgroup's first dst element
-    const long long j0 = row_of(e0, F.width, F.inv_w);
-    const uint32_t r = (uint32_t)(e0 - j0 * (long long)F.width) + threadIdx.x * kUnit;  // < width + 1024
-    const uint32_t q = r / F.width;
-    long long j = j0 + q;            // dst row and column of this thread's first unit
-    uint32_t c = r - q * F.width;
+    UnitAt here = first_unit<kUnit>(F.w, u0);  // in dst
     uint32_t idx[kUnroll], col[kUnroll];
 #pragma unroll
     for (int i = 0; i < kUnroll; i++) {  // every index load issued before any is used
         const long long u = u0 + i * kBlock + threadIdx.x;
-        // a gathered unit (u < F.kept) has j < k; entry 0 exists (keep is passed only where k >= 1)
+        // a gathered unit (u < F.kept) has here.j < k; entry 0 exists (keep is passed only where k >= 1)
         if constexpr (kClone) {
-            // an appended unit (F.kept <= u < F.units) has k <= j < k + n_append; entry 0 of from_list exists
+            // an appended unit (F.kept <= u < F.units) has k <= here.j < k + n_append; entry 0 of from_list exists
             // (a field is cloned only where n_append >= 1) and serves the lanes past the last unit
             const bool gathered = kKeep && u < F.kept;
             const uint32_t* list = gathered ? keep : from_list;
-            const long long entry = gathered ? j : (u >= F.kept && u < F.units ? j - k : 0);
+            const long long entry = gathered ? here.j : (u >= F.kept && u < F.units ? here.j - k : 0);
             const uint32_t got = list[entry];
-            idx[i] = (!kKeep && u < F.kept) ? (uint32_t)j : got;
+            idx[i] = (!kKeep && u < F.kept) ? (uint32_t)here.j : got;
         } else {
-            idx[i] = kKeep ? keep[u < F.kept ? j : 0] : (uint32_t)j;
+            idx[i] = kKeep ? keep[u < F.kept ? here.j : 0] : (uint32_t)here.j;
         }
-        col[i] = c;
-        c += F.step_c;
-        j += F.step_j;
-        if (c >= F.width) {
-            c -= F.width;
-            j++;
-        }
+        col[i] = here.c;
+        next_unit(F.w, here);
     }
     const V* from[kUnroll];          // where the unit is read: F.safe where it is zeros, so the loads need no branch
     bool zero[kUnroll];
@@ -338,7 +366,8 @@ __device__ __forceinline__ void resize_units(const ResizeField& F, long long u0,
         const bool in_src = (u < (kClone ? F.units : F.kept)) & ((long long)idx[i] < F.n_rows);
         const bool in_append = !kClone & (u >= F.kept) & (u < F.units) & (F.append != nullptr);
         const uint32_t* base = in_src ? F.src : (in_append ? F.append : F.safe);
-        const size_t at = in_src ? ((size_t)idx[i] * F.width + col[i]) / kUnit : (in_append ? (size_t)(u - F.kept) : 0);
+        const size_t at =
+            in_src ? ((size_t)idx[i] * F.w.width + col[i]) / kUnit : (in_append ? (size_t)(u - F.kept) : 0);
         from[i] = reinterpret_cast<const V*>(base) + at;
         zero[i] = !(in_src | in_append);
     }
@@ -365,84 +394,55 @@ __device__ __forceinline__ void zero_units(const ResizeField& F, long long u0)
     }
 }
 
-__global__ __launch_bounds__(kBlock) void resize_rows_kernel(const ResizeBatch batch, const uint32_t* __restrict__ keep)
+// The instance of resize_units for the launch's keep list (workgroup-uniform: given or not) and the field's unit.
+template <bool kClone>
+__device__ __forceinline__ void resize_field_units(const ResizeField& F, long long u0,
+                                                   const uint32_t* __restrict__ keep,
+                                                   const uint32_t* __restrict__ from, long long k)
+{
+    if (keep) {
+        if (F.w.unit == 4)
+            resize_units<u32x4, true, kClone>(F, u0, keep, from, k);
+        else
+            resize_units<uint32_t, true, kClone>(F, u0, keep, from, k);
+    } else {
+        if (F.w.unit == 4)
+            resize_units<u32x4, false, kClone>(F, u0, keep, from, k);
+        else
+            resize_units<uint32_t, false, kClone>(F, u0, keep, from, k);
+    }
+}
+
+// kCloning (include/hidegs_clone.h): the launch has cloned fields.  Bit f of `cloned` says that field f of the
+// batch takes its appended rows from src, row from[i] for dst row k + i; the mode is workgroup-uniform like the
+// descriptor.  Without kCloning there is no such field and from, k and cloned are not read.
+template <bool kCloning>
+__global__ __launch_bounds__(kBlock) void resize_kernel(const Batch<ResizeField> batch,
+                                                        const uint32_t* __restrict__ keep,
+                                                        const uint32_t* __restrict__ from, long long k, uint32_t cloned)
 {
     // workgroup-uniform selects over constant indices: the descriptors stay in scalar registers
     ResizeField F = batch.f[0];
     int first = batch.first[0];
+    bool clone = kCloning && (cloned & 1u);
 #pragma unroll
     for (int i = 1; i < kMaxFields; i++) {
         if (i < batch.count && (int)blockIdx.x >= batch.first[i]) {
             F = batch.f[i];
             first = batch.first[i];
+            if (kCloning) clone = (cloned >> i) & 1u;
         }
     }
     const long long u0 = (long long)((int)blockIdx.x - first) * kUnitsPerBlock;
     if (!F.safe) {
-        if (F.unit == 4)
-            zero_units<u32x4>(F, u0);
-        else
-            zero_units<uint32_t>(F, u0);
-    } else if (keep) {
-        if (F.unit == 4)
-            resize_units<u32x4, true>(F, u0, keep);
-        else
-            resize_units<uint32_t, true>(F, u0, keep);
-    } else {
-        if (F.unit == 4)
-            resize_units<u32x4, false>(F, u0, keep);
-        else
-            resize_units<uint32_t, false>(F, u0, keep);
-    }
-}
-
-// resize_rows_kernel with a third source for the appended rows (include/hidegs_clone.h): bit f of `cloned` says
-// that field f of the batch takes them from src, row from[i] for dst row k + i.  The mode is workgroup-uniform
-// like the descriptor; the other fields run the code of resize_rows_kernel.
-__global__ __launch_bounds__(kBlock) void resize_rows_cloned_kernel(const ResizeBatch batch,
-                                                                    const uint32_t* __restrict__ keep,
-                                                                    const uint32_t* __restrict__ from, long long k,
-                                                                    uint32_t cloned)
-{
-    ResizeField F = batch.f[0];
-    int first = batch.first[0];
-    bool clone = cloned & 1u;
-#pragma unroll
-    for (int i = 1; i < kMaxFields; i++) {
-        if (i < batch.count && (int)blockIdx.x >= batch.first[i]) {
-            F = batch.f[i];
-            first = batch.first[i];
-            clone = (cloned >> i) & 1u;
-        }
-    }
-    const long long u0 = (long long)((int)blockIdx.x - first) * kUnitsPerBlock;
-    if (!F.safe) {
-        if (F.unit == 4)
+        if (F.w.unit == 4)
             zero_units<u32x4>(F, u0);
         else
             zero_units<uint32_t>(F, u0);
     } else if (clone) {
-        if (keep) {
-            if (F.unit == 4)
-                resize_units<u32x4, true, true>(F, u0, keep, from, k);
-            else
-                resize_units<uint32_t, true, true>(F, u0, keep, from, k);
-        } else {
-            if (F.unit == 4)
-                resize_units<u32x4, false, true>(F, u0, keep, from, k);
-            else
-                resize_units<uint32_t, false, true>(F, u0, keep, from, k);
-        }
-    } else if (keep) {
-        if (F.unit == 4)
-            resize_units<u32x4, true>(F, u0, keep);
-        else
-            resize_units<uint32_t, true>(F, u0, keep);
+        resize_field_units<kCloning>(F, u0, keep, from, k);
     } else {
-        if (F.unit == 4)
-            resize_units<u32x4, false>(F, u0, keep);
-        else
-            resize_units<uint32_t, false>(F, u0, keep);
+        resize_field_units<false>(F, u0, keep, from, k);
     }
 }
 
@@ -456,111 +456,67 @@ ResizeField resize_field(const float* src, const float* append, float* dst, long
     F.safe = F.src ? F.src : F.append;
     F.dst = reinterpret_cast<uint32_t*>(dst);
     F.n_rows = n_rows;
-    F.width = (uint32_t)width;
     // width a multiple of 4 and every base on 16 bytes: every row start and every quad is aligned, and
     // k * width is a multiple of 4, so no quad holds both gathered and appended floats
-    F.unit = (width % 4 == 0 && aligned16(F.src) && aligned16(F.append) && aligned16(dst)) ? 4u : 1u;
-    F.kept = k * (long long)width / F.unit;
-    F.units = (k + n_append) * (long long)width / F.unit;
-    F.step_j = (uint32_t)(kBlock * F.unit) / F.width;
-    F.step_c = (uint32_t)(kBlock * F.unit) % F.width;
-    F.inv_w = 1.0 / (double)width;
+    F.w = make_walk(width, (width % 4 == 0 && aligned16(F.src) && aligned16(F.append) && aligned16(dst)) ? 4u : 1u);
+    F.kept = k * (long long)width / F.w.unit;
+    F.units = (k + n_append) * (long long)width / F.w.unit;
     return F;
 }
 
-int resize_rows(const hidegs_resize_field* fields, int nfields, const uint32_t* keep, long long k, long long n_append,
-                hipStream_t stream)
-{
-    const std::string who = "resize_rows";
-    if (nfields < 0) return fail(HIDEGS_E_ARG, who + ": negative field count");
-    if (k < 0 || n_append < 0 || k > kSelectMax || n_append > kSelectMax || k + n_append > kSelectMax)
-        return fail(HIDEGS_E_ARG, who + ": k, n_append and k + n_append must be in [0, 2^31)");
-    if (nfields > 0 && !fields) return fail(HIDEGS_E_ARG, who + ": NULL field list");
-    for (int i = 0; i < nfields; i++) {
-        if (fields[i].width < 1) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": width < 1");
-        if (fields[i].n_rows < 0) return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": negative n_rows");
-    }
-    if (k + n_append == 0 || nfields == 0) return 0;
-    for (int i = 0; i < nfields; i++) {
-        if (!fields[i].dst || (k > 0 && fields[i].n_rows > 0 && !fields[i].src))
-            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": NULL pointer");
-        if (!keep && k > fields[i].n_rows)
-            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": without keep, k must not exceed n_rows");
-    }
-    if (k == 0) keep = nullptr;  // no row is gathered: the kernel reads no entry
-    for (int i0 = 0; i0 < nfields; i0 += kMaxFields) {  // kMaxFields per launch
-        ResizeBatch batch;
-        batch.count = 0;
-        long long blocks = 0;
-        for (int i = i0; i < nfields && i < i0 + kMaxFields; i++) {
-            const hidegs_resize_field& a = fields[i];
-            const ResizeField F = resize_field(k > 0 && a.n_rows > 0 ? a.src : nullptr, n_append > 0 ? a.append : nullptr,
-                                               a.dst, a.n_rows, a.width, k, n_append);
-            batch.first[batch.count] = (int)blocks;
-            batch.f[batch.count++] = F;
-            blocks += (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
-            if (blocks > 0x7fffffffLL) return fail(HIDEGS_E_ARG, who + ": fields too large for one launch");
-        }
-        batch.first[batch.count] = (int)blocks;
-        HIDEGS_LAUNCH("resize_rows", resize_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch, keep);
-    }
-    return check_launch("resize_rows", stream, 0);
-}
+bool is_cloned(const hidegs_resize_field&) { return false; }
+bool is_cloned(const hidegs_clone_field& a) { return a.cloned != 0; }
 
-// hidegs_resize_rows_cloned.  A batch without a cloned field is a launch of resize_rows_kernel itself.
-int resize_rows_cloned(const hidegs_clone_field* fields, int nfields, const uint32_t* keep, long long k,
-                       const uint32_t* from, long long n_append, hipStream_t stream)
+// hidegs_resize_rows and hidegs_resize_rows_cloned, `name` without its prefix; the first has no cloned field
+// and no `from`.  A batch without a cloned field is a launch of resize_kernel<false>, whichever entry was called.
+template <typename Field>
+int resize_rows(const char* name, const Field* fields, int nfields, const uint32_t* keep, long long k,
+                const uint32_t* from, long long n_append, hipStream_t stream)
 {
-    const std::string who = "resize_rows_cloned";
+    const std::string who = name;
     if (nfields < 0) return fail(HIDEGS_E_ARG, who + ": negative field count");
     if (k < 0 || n_append < 0 || k > kSelectMax || n_append > kSelectMax || k + n_append > kSelectMax)
         return fail(HIDEGS_E_ARG, who + ": k, n_append and k + n_append must be in [0, 2^31)");
     if (nfields > 0 && !fields) return fail(HIDEGS_E_ARG, who + ": NULL field list");
     bool any_cloned = false;
     for (int i = 0; i < nfields; i++) {
-        const std::string field = who + ": field " + std::to_string(i);
-        if (fields[i].width < 1) return fail(HIDEGS_E_ARG, field + ": width < 1");
-        if (fields[i].n_rows < 0) return fail(HIDEGS_E_ARG, field + ": negative n_rows");
-        if (fields[i].cloned && fields[i].append) return fail(HIDEGS_E_ARG, field + ": cloned, but append is given");
-        any_cloned = any_cloned || fields[i].cloned;
+        if (int rc = check_shape(who, i, fields[i])) return rc;
+        if (is_cloned(fields[i]) && fields[i].append)
+            return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": cloned, but append is given");
+        any_cloned = any_cloned || is_cloned(fields[i]);
     }
     if (k + n_append == 0 || nfields == 0) return 0;
-    const bool cloning = any_cloned && n_append > 0;
+    // the source of field `a` is read: for its kept rows, or for its cloned ones
+    const auto reads_src = [&](const Field& a) { return a.n_rows > 0 && (k > 0 || (is_cloned(a) && n_append > 0)); };
     for (int i = 0; i < nfields; i++) {
-        const hidegs_clone_field& a = fields[i];
-        const bool reads_src = a.n_rows > 0 && (k > 0 || (a.cloned && n_append > 0));
-        if (!a.dst || (reads_src && !a.src))
+        const Field& a = fields[i];
+        if (!a.dst || (reads_src(a) && !a.src))
             return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": NULL pointer");
         if (!keep && k > a.n_rows)
             return fail(HIDEGS_E_ARG, who + ": field " + std::to_string(i) + ": without keep, k must not exceed n_rows");
     }
-    if (cloning && !from) return fail(HIDEGS_E_ARG, who + ": NULL from with a cloned field");
+    if (any_cloned && n_append > 0 && !from) return fail(HIDEGS_E_ARG, who + ": NULL from with a cloned field");
     if (k == 0) keep = nullptr;  // no row is gathered by keep: the kernel reads no entry
     for (int i0 = 0; i0 < nfields; i0 += kMaxFields) {  // kMaxFields per launch
-        ResizeBatch batch;
-        batch.count = 0;
-        long long blocks = 0;
+        Batch<ResizeField> batch;
         uint32_t cloned = 0;
         for (int i = i0; i < nfields && i < i0 + kMaxFields; i++) {
-            const hidegs_clone_field& a = fields[i];
-            const bool clone = a.cloned && n_append > 0;
+            const Field& a = fields[i];
+            if (is_cloned(a) && n_append > 0) cloned |= 1u << batch.count;
             // a cloned field has no append side: 16-byte units where src and dst allow
-            const ResizeField F = resize_field((k > 0 || clone) && a.n_rows > 0 ? a.src : nullptr,
-                                               n_append > 0 ? a.append : nullptr, a.dst, a.n_rows, a.width, k, n_append);
-            if (clone) cloned |= 1u << batch.count;
-            batch.first[batch.count] = (int)blocks;
-            batch.f[batch.count++] = F;
-            blocks += (F.units + kUnitsPerBlock - 1) / kUnitsPerBlock;
-            if (blocks > 0x7fffffffLL) return fail(HIDEGS_E_ARG, who + ": fields too large for one launch");
+            const ResizeField F = resize_field(reads_src(a) ? a.src : nullptr, n_append > 0 ? a.append : nullptr, a.dst,
+                                               a.n_rows, a.width, k, n_append);
+            if (int rc = place_field(batch, F, who)) return rc;
         }
-        batch.first[batch.count] = (int)blocks;
+        const dim3 grid((unsigned)batch.first[batch.count]);
         if (cloned)
-            HIDEGS_LAUNCH("resize_rows_cloned", resize_rows_cloned_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                          batch, keep, from, k, cloned);
+            HIDEGS_LAUNCH("resize_rows_cloned", resize_kernel<true>, grid, dim3(kBlock), 0, stream, batch, keep, from,
+                          k, cloned);
         else
-            HIDEGS_LAUNCH("resize_rows", resize_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, batch, keep);
+            HIDEGS_LAUNCH("resize_rows", resize_kernel<false>, grid, dim3(kBlock), 0, stream, batch, keep,
+                          (const uint32_t*)nullptr, 0LL, 0u);
     }
-    return check_launch("resize_rows_cloned", stream, 0);
+    return check_launch(name, stream, 0);
 }
 
 }  // namespace
@@ -612,12 +568,13 @@ extern "C" int hidegs_resize_rows(const hidegs_resize_field* fields, int nfields
                                   long long n_append, void* stream)
 {
     if (int rc = hidegs::take_async_error("hidegs_resize_rows", hidegs::as_stream(stream))) return rc;
-    return hidegs::resize_rows(fields, nfields, keep, k, n_append, hidegs::as_stream(stream));
+    return hidegs::resize_rows("resize_rows", fields, nfields, keep, k, nullptr, n_append, hidegs::as_stream(stream));
 }
 
 extern "C" int hidegs_resize_rows_cloned(const hidegs_clone_field* fields, int nfields, const uint32_t* keep, long long k,
                                          const uint32_t* from, long long n_append, void* stream)
 {
     if (int rc = hidegs::take_async_error("hidegs_resize_rows_cloned", hidegs::as_stream(stream))) return rc;
-    return hidegs::resize_rows_cloned(fields, nfields, keep, k, from, n_append, hidegs::as_stream(stream));
+    return hidegs::resize_rows("resize_rows_cloned", fields, nfields, keep, k, from, n_append,
+                               hidegs::as_stream(stream));
 }

@@ -173,23 +173,15 @@ def resize_rows(tensors: Sequence[torch.Tensor], keep: Optional[torch.Tensor] = 
         outs = [torch.empty((k + a, *t.shape[1:]), dtype=torch.float32, device=dev) for t in tensors]
         if k + a == 0:
             return outs
-        if clone is None:
-            fields = (_lib.ResizeField * len(tensors))()
-            for f, t, new, out in zip(fields, tensors, given, outs):
-                f.src, f.append, f.dst = _lib.ptr(t), _lib.ptr(new), _lib.ptr(out)
-                f.n_rows, f.width = n, out[0].numel()
-            rc = _lib.lib().hidegs_resize_rows(C.cast(fields, C.c_void_p), len(tensors), _lib.ptr(indices), k, a,
-                                               _lib.stream_handle(dev))
-            _lib.check(rc, "resize_rows")
-            return outs
-        # the tiled index list, built on the device: 4 B per appended row
-        if clone_mask:
-            rows = picked[:m] if picked is not None else torch.empty(0, dtype=torch.int32, device=dev)
-        elif clone.dtype == torch.int64:  # an entry outside [0, n) must stay outside as 32 bits
-            rows = torch.where((clone < 0) | (clone >= n), -1, clone).to(torch.int32)
-        else:
-            rows = clone  # a negative int32 is >= 2^31 as the kernel reads it
-        rows = rows.repeat(repeats) if repeats > 1 else rows.contiguous()
+        rows = None  # without clone no field is cloned, and the call takes no index list for the appended rows
+        if clone is not None:  # the tiled index list, built on the device: 4 B per appended row
+            if clone_mask:
+                rows = picked[:m] if picked is not None else torch.empty(0, dtype=torch.int32, device=dev)
+            elif clone.dtype == torch.int64:  # an entry outside [0, n) must stay outside as 32 bits
+                rows = torch.where((clone < 0) | (clone >= n), -1, clone).to(torch.int32)
+            else:
+                rows = clone  # a negative int32 is >= 2^31 as the kernel reads it
+            rows = rows.repeat(repeats) if repeats > 1 else rows.contiguous()
         fields = (_lib.CloneField * len(tensors))()
         for f, t, new, out in zip(fields, tensors, append, outs):
             f.src, f.dst = _lib.ptr(t), _lib.ptr(out)

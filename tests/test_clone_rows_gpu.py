@@ -1,5 +1,5 @@
 """Cloning rows inside the resize on the GPU (include/hidegs_clone.h, hidegs_amd/csrc/rows.hip
-resize_rows_cloned_kernel; hidegs_amd.resize `clone` / `repeats` / `CLONED`, Adam.resize_rows) against the torch
+resize_kernel<true>; hidegs_amd.resize `clone` / `repeats` / `CLONED`, Adam.resize_rows) against the torch
 ops that define it -- torch.cat((t[keep], torch.cat([t[idx]] * repeats))), the given rows or zeros per field, on
 the same device -- bit for bit: every comparison is torch.equal on the int32 view, so NaN payloads and -0.0
 must survive.  A workgroup owns 2048 units, so a few thousand rows reach every path.
@@ -125,7 +125,7 @@ def test_cloned_given_and_zero_fields_interleaved_over_two_launches(built_lib):
     given = [payload(f)[n:n + a].clone() for f in range(10)]
     # field 8 is the first of the second launch
     for modes, counts in [("CGZCGZZGCZ", (2, 0)), ("ZGZCGZZGCG", (2, 0)),
-                          ("CGZGGZZZGZ", (1, 1))]:  # no cloned field in the second launch: resize_rows_kernel itself
+                          ("CGZGGZZZGZ", (1, 1))]:  # no cloned field in the second launch: resize_kernel<false>
         new = [{"C": CLONED, "G": given[f], "Z": None}[c] for f, c in enumerate(modes)]
         with _lib.kernel_timer() as kt:
             outs = resize_rows(tensors, keep, new, clone=clone, repeats=r)

@@ -187,6 +187,47 @@ def test_an_index_past_the_rows_gives_a_zero_row(built_lib):
         assert not bits(dst[k:]).any()
 
 
+@pytest.mark.parametrize("with_keep", [True, False])
+def test_both_entry_points_write_the_same_bits_for_plain_fields(built_lib, with_keep):
+    """hidegs_resize_rows and hidegs_resize_rows_cloned with cloned = 0 in every field share one host path: the
+    same dst bits, torch's cat((src[keep], append or zeros)), and launches named resize_rows only.  Width 3 (scalar
+    path), width 4 (16-byte path) and width 4 without append; k = 2049 rows of width 4 put the seam between
+    gathered and appended units one unit into a workgroup's second."""
+    n, k, a = 3000, 2049, 300
+    assert k * 4 // 4 == UNITS_PER_WORKGROUP + 1
+    srcs = [payload(1)[:n].clone(), payload(2)[:n].clone(), payload(7)[:n].clone()]
+    news = [payload(1)[n:n + a].clone(), payload(2)[n:n + a].clone(), None]
+    assert [s.shape[1] for s in srcs] == [3, 4, 4] and all(t.data_ptr() % 16 == 0 for t in srcs + news[:2])
+    keep = None
+    if with_keep:
+        keep = torch.randperm(n, generator=torch.Generator().manual_seed(9))[:k].sort().values.to(torch.int32).cuda()
+    want = [torch.cat((s[:k] if keep is None else s[keep.long()], torch.zeros(a, s.shape[1], device="cuda") if new is None
+                       else new)) for s, new in zip(srcs, news)]
+    stream = _lib.stream_handle(srcs[0].device)
+    got = {}
+    for entry, struct in (("hidegs_resize_rows", _lib.ResizeField), ("hidegs_resize_rows_cloned", _lib.CloneField)):
+        fields = (struct * len(srcs))()
+        dsts = [torch.empty(k + a, s.shape[1], device="cuda") for s in srcs]
+        for f, src, new, dst in zip(fields, srcs, news, dsts):
+            bits(dst).fill_(FILL)
+            f.src, f.append, f.dst, f.n_rows, f.width = src.data_ptr(), _lib.ptr(new), dst.data_ptr(), n, dst.shape[1]
+            if struct is _lib.CloneField:
+                f.cloned = 0
+        args = (ctypes.cast(fields, ctypes.c_void_p), len(srcs), _lib.ptr(keep), k)
+        with _lib.kernel_timer() as kt:
+            if struct is _lib.CloneField:
+                rc = built_lib.hidegs_resize_rows_cloned(*args, None, a, stream)
+            else:
+                rc = built_lib.hidegs_resize_rows(*args, a, stream)
+            _lib.check(rc, entry)
+            torch.cuda.synchronize()
+        assert kt.get("resize_rows")[1] == 1 and kt.get("resize_rows_cloned")[1] == 0, entry
+        got[entry] = dsts
+    for f, (plain, cloned, exp) in enumerate(zip(got["hidegs_resize_rows"], got["hidegs_resize_rows_cloned"], want)):
+        assert same_bits(plain, cloned), f"field {f}: the two entry points differ"
+        assert same_bits(plain, exp), f"field {f}: not torch's result"
+
+
 # ---- rows wider than a workgroup step -------------------------------------------------------------------
 def wide_sources():
     """test_rows_gpu's wide fields: nine (37, w) sources, w from 255 to 2052, the 16-byte path's on 16 bytes and

@@ -46,8 +46,10 @@
 #include "../../include/hidegs_nearest_k.h"
 #include "../../include/hidegs_nearest_within.h"
 #include "../../include/hidegs_nearest_lists.h"
+#include "../../include/hidegs_components.h"
 #include "common.h"
 #include "morton_tree.h"
+#include "union_find.h"
 
 namespace hidegs {
 namespace {
@@ -578,6 +580,7 @@ dim3 hard_grid(long long Q) { return dim3(std::min<unsigned>(kHardGrid, (unsigne
 #include "nearest_k.h"
 #include "nearest_within.h"
 #include "nearest_lists.h"
+#include "nearest_components.h"
 
 }  // namespace
 }  // namespace hidegs
@@ -705,4 +708,13 @@ extern "C" int hidegs_nearest_list_fill(const void* index, size_t index_bytes, l
 {
     return hidegs::list_fill(index, index_bytes, P, scratch, scratch_bytes, queries, Q, r2, exclude, starts, capacity, rows_out,
                              dist2_out, stream);
+}
+
+extern "C" size_t hidegs_nearest_components_within_scratch_bytes(long long) { return 0; }
+
+extern "C" int hidegs_nearest_components_within(const void* index, size_t index_bytes, long long P, void* scratch,
+                                                size_t scratch_bytes, const float* r2, int r2_is_per_row, int32_t* parent,
+                                                void* stream)
+{
+    return hidegs::components_within(index, index_bytes, P, scratch, scratch_bytes, r2, r2_is_per_row, parent, stream);
 }

@@ -12,15 +12,14 @@ Everything runs on the current stream with no host synchronisation and can be ca
 """
 from __future__ import annotations
 
-import numbers
 from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _wrap
 from .nearest import NearestIndex, NeighborLists
 
-_MAX = (1 << 31) - 1
+_need = _wrap.Checks("moments")
 _scratch = {}  # (device, stream) -> uint8 tensor: the long list of the list form, for calls outside a capture
 
 
@@ -33,39 +32,6 @@ class Moments(NamedTuple):
     cov: torch.Tensor
     evals: Optional[torch.Tensor]
     evecs: Optional[torch.Tensor]
-
-
-def _need_tensor(t, what: str, dtype, shape_text: str, ok) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"moments: {what} is not a tensor")
-    if t.dtype != dtype or not ok(t) or not t.is_contiguous():
-        raise RuntimeError(f"moments: {what}: expected a contiguous {shape_text} {dtype} tensor, got {t.dtype} of shape "
-                           f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
-
-
-def _need_gpu(**tensors) -> torch.device:
-    dev = None
-    for what, t in tensors.items():
-        if t.device.type != "cuda":
-            raise RuntimeError(f"moments: {what}: expected a GPU tensor, got one on {t.device}")
-        if dev is None:
-            dev = t.device
-        elif t.device != dev:
-            raise RuntimeError(f"moments: tensors on different devices: {next(iter(tensors))} on {dev}, {what} on {t.device}")
-    return dev
-
-
-def _scratch_for(device, stream, need: int) -> torch.Tensor:
-    """The scratch of one call of the list form.  Outside a capture it is kept per device and stream (calls on one
-    stream run one after the other, so they can share it).  A call that is being captured into a graph gets a
-    tensor of its own from the graph's memory pool and nothing is kept: a kept tensor would be shared by every
-    later graph captured on the same stream, and two such graphs replayed on different streams would race on it."""
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(need, dtype=torch.uint8, device=device)
-    tmp = _scratch.get((device, stream))
-    if tmp is None or tmp.numel() < need:
-        tmp = _scratch[(device, stream)] = torch.empty(need, dtype=torch.uint8, device=device)
-    return tmp
 
 
 def neighbor_moments(points: torch.Tensor, neighbors, weights: torch.Tensor = None, eigen: bool = False,
@@ -84,33 +50,14 @@ def neighbor_moments(points: torch.Tensor, neighbors, weights: torch.Tensor = No
     The additions follow a fixed order (blocks of 64 positions, every block a sequential sum, then the blocks in
     order): the same list gives the same bits whatever else the call holds.  Runs on the current stream; no
     host synchronisation."""
-    _need_tensor(points, "points", torch.float32, "(P, 3)", lambda t: t.dim() == 2 and t.shape[1] == 3)
-    P = points.shape[0]
-    if P > _MAX:
-        raise RuntimeError("moments: points: at most 2^31 - 1 rows")
-    named = {"points": points}
+    P = _need.cloud(points, "points")
     lists = isinstance(neighbors, NeighborLists)
-    if lists:
-        _need_tensor(neighbors.starts, "neighbors.starts", torch.int32, "(Q + 1,)", lambda t: t.dim() == 1 and t.numel() >= 1)
-        _need_tensor(neighbors.rows, "neighbors.rows", torch.int32, "1-D", lambda t: t.dim() == 1)
-        Q = neighbors.starts.numel() - 1
-        named.update({"neighbors.starts": neighbors.starts, "neighbors.rows": neighbors.rows})
-    else:
-        _need_tensor(neighbors, "neighbors", torch.int32, "(Q, k), k >= 1,",
-                     lambda t: t.dim() == 2 and t.shape[1] >= 1)
-        Q, k = neighbors.shape
-        if k > _MAX:
-            raise RuntimeError("moments: neighbors: at most 2^31 - 1 columns")
-        named["neighbors"] = neighbors
-    if Q > _MAX:
-        raise RuntimeError("moments: neighbors: at most 2^31 - 1 queries")
+    Q, named = _need.neighbors(neighbors, lists)
+    named = {"points": points, **named}
     if weights is not None:
-        _need_tensor(weights, "weights", torch.float32, "(P,)", lambda t: t.dim() == 1)
-        if weights.numel() != P:
-            raise RuntimeError(f"moments: weights has {weights.numel()} entries, points has {P} rows")
+        _need.per_row(weights, "weights", torch.float32, P, "points has {} rows", "(P,)")
         named["weights"] = weights
-    if not isinstance(eigen, bool):
-        raise RuntimeError(f"moments: eigen must be a bool, got {type(eigen).__name__}")
+    _need.flag(eigen, "eigen")
     want = (("count", torch.int32, (Q,)), ("mean", torch.float32, (Q, 3)), ("cov", torch.float32, (Q, 6)),
             ("evals", torch.float32, (Q, 3)), ("evecs", torch.float32, (Q, 3, 3)))
     if out is not None:
@@ -121,9 +68,9 @@ def neighbor_moments(points: torch.Tensor, neighbors, weights: torch.Tensor = No
                 if t is not None:
                     raise RuntimeError(f"moments: out {what} must be None without eigen")
                 continue
-            _need_tensor(t, f"out {what}", dtype, str(shape), lambda t, shape=shape: tuple(t.shape) == shape)
+            _need.tensor(t, f"out {what}", dtype, shape, lambda t, shape=shape: tuple(t.shape) == shape)
             named[f"out {what}"] = t
-    dev = _need_gpu(**named)
+    dev = _need.gpu(None, **named)
     with torch.cuda.device(dev):
         if out is not None:
             count, mean, cov, evals, evecs = out
@@ -139,13 +86,14 @@ def neighbor_moments(points: torch.Tensor, neighbors, weights: torch.Tensor = No
         tail = (count.data_ptr(), mean.data_ptr(), cov.data_ptr(), evals.data_ptr() if eigen else None,
                 evecs.data_ptr() if eigen else None, stream)
         if lists:
-            tmp = _scratch_for(dev, stream, L.hidegs_neighbor_moments_scratch_bytes(Q))
+            tmp = _wrap.stream_scratch(_scratch, dev, stream, L.hidegs_neighbor_moments_scratch_bytes(Q))
             rc = L.hidegs_neighbor_moments_lists(tmp.data_ptr(), tmp.numel(), _lib.ptr(points), _lib.ptr(weights), P,
                                                  neighbors.starts.data_ptr(), _lib.ptr(neighbors.rows),
                                                  neighbors.rows.numel(), Q, *tail)
             _lib.check(rc, "neighbor_moments_lists")
         else:
-            rc = L.hidegs_neighbor_moments_table(_lib.ptr(points), _lib.ptr(weights), P, neighbors.data_ptr(), Q, k, *tail)
+            rc = L.hidegs_neighbor_moments_table(_lib.ptr(points), _lib.ptr(weights), P, neighbors.data_ptr(), Q, neighbors.shape[1],
+                                                 *tail)
             _lib.check(rc, "neighbor_moments_table")
     return res
 
@@ -157,18 +105,18 @@ def sym3_eigen(cov: torch.Tensor, out: Tuple[torch.Tensor, torch.Tensor] = None)
     magnitude is positive; row 2 has the sign that makes the matrix a rotation (det = +1).  A matrix with a NaN or
     an infinity gives NaN everywhere.  out=(evals, evecs) reuses two such tensors.  Runs on the current stream;
     no host synchronisation."""
-    _need_tensor(cov, "cov", torch.float32, "(Q, 6)", lambda t: t.dim() == 2 and t.shape[1] == 6)
+    _need.tensor(cov, "cov", torch.float32, "(Q, 6)", lambda t: t.dim() == 2 and t.shape[1] == 6)
     Q = cov.shape[0]
-    if Q > _MAX:
+    if Q > _wrap.MAX:
         raise RuntimeError("moments: cov: at most 2^31 - 1 rows")
     named = {"cov": cov}
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 2:
             raise RuntimeError("moments: out must be a pair (evals, evecs)")
-        _need_tensor(out[0], "out evals", torch.float32, f"({Q}, 3)", lambda t: tuple(t.shape) == (Q, 3))
-        _need_tensor(out[1], "out evecs", torch.float32, f"({Q}, 3, 3)", lambda t: tuple(t.shape) == (Q, 3, 3))
+        _need.tensor(out[0], "out evals", torch.float32, (Q, 3), lambda t: tuple(t.shape) == (Q, 3))
+        _need.tensor(out[1], "out evecs", torch.float32, (Q, 3, 3), lambda t: tuple(t.shape) == (Q, 3, 3))
         named.update({"out evals": out[0], "out evecs": out[1]})
-    dev = _need_gpu(**named)
+    dev = _need.gpu(None, **named)
     with torch.cuda.device(dev):
         evals, evecs = out if out is not None else (torch.empty((Q, 3), dtype=torch.float32, device=dev),
                                                     torch.empty((Q, 3, 3), dtype=torch.float32, device=dev))
@@ -182,17 +130,14 @@ def point_frames(points: torch.Tensor, k: int, index: NearestIndex = None, weigh
     """The local frame of every point: the moments and principal axes of its k nearest points, itself included
     (1 <= k <= 64).  index: a NearestIndex over `points`, or None to build one.  It is
     neighbor_moments(points, index.query_k(points, k)[0], weights, eigen=True)."""
-    _need_tensor(points, "points", torch.float32, "(P, 3)", lambda t: t.dim() == 2 and t.shape[1] == 3)
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= 64:
-        raise RuntimeError(f"moments: k must be an integer in [1, 64], got {k!r}")
+    _need.tensor(points, "points", torch.float32, "(P, 3)", _wrap.is_cloud)  # how many rows is NearestIndex's to judge
+    k = _need.integer(k, "k", 1, 64, "an integer in [1, 64]")
     if index is not None and not isinstance(index, NearestIndex):
         raise RuntimeError(f"moments: index must be a NearestIndex or None, got {type(index).__name__}")
     if weights is not None:
-        _need_tensor(weights, "weights", torch.float32, "(P,)", lambda t: t.dim() == 1)
-        if weights.numel() != points.shape[0]:
-            raise RuntimeError(f"moments: weights has {weights.numel()} entries, points has {points.shape[0]} rows")
-    _need_gpu(points=points, **({} if weights is None else {"weights": weights}))
+        _need.per_row(weights, "weights", torch.float32, points.shape[0], "points has {} rows", "(P,)")
+    _need.gpu(None, points=points, **({} if weights is None else {"weights": weights}))
     if index is None:
         index = NearestIndex(points)
-    idx, _ = index.query_k(points, int(k))
+    idx, _ = index.query_k(points, k)
     return neighbor_moments(points, idx, weights=weights, eigen=True)

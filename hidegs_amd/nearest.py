@@ -21,101 +21,66 @@ The index holds its own copy of the points: rebuild it after the positions move 
 """
 from __future__ import annotations
 
-import numbers
 from typing import Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _wrap
 
-_MAX = (1 << 31) - 1
 K_MAX = 64  # of query_k and query_within
+_need = _wrap.Checks("nearest", "the index")
 
 
 def _need_rows(t, what: str) -> int:
     """`t` is a contiguous (n, 3) float32 tensor; returns n."""
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"nearest: {what} is not a tensor")
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
-        raise RuntimeError(f"nearest: {what}: expected a contiguous (n, 3) float32 tensor, got {t.dtype} of shape "
-                           f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
-    if t.shape[0] > _MAX:
-        raise RuntimeError(f"nearest: {what}: at most 2^31 - 1 rows")
-    return t.shape[0]
-
-
-def _need_gpu(dev: torch.device, **tensors) -> None:
-    for what, t in tensors.items():
-        if t.device.type != "cuda":
-            raise RuntimeError(f"nearest: {what}: expected a GPU tensor, got one on {t.device}")
-        if dev is not None and t.device != dev:
-            raise RuntimeError(f"nearest: tensors on different devices: the index on {dev}, {what} on {t.device}")
+    return _need.cloud(t, what, "a contiguous (n, 3) float32 tensor")
 
 
 def _size_class(q: int) -> int:
     """The power of two at or above q, 1024 at least and 2^31 - 1 at most (the largest Q there is): one scratch
     tensor serves every size of its class."""
-    return min(max(1024, 1 << (q - 1).bit_length()), _MAX)
+    return min(max(1024, 1 << (q - 1).bit_length()), _wrap.MAX)
 
 
 def _need_k(k, least: int) -> int:
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
-        raise RuntimeError(f"nearest: k must be an integer, got {type(k).__name__}")
-    k = int(k)
-    if not least <= k <= K_MAX:
-        raise RuntimeError(f"nearest: k must be in [{least}, {K_MAX}], got {k}")
-    return k
+    return _need.integer(k, "k", least, K_MAX, "an integer", span=f"[{least}, {K_MAX}]")
 
 
 def _need_exclude(exclude, Q: int) -> dict:
     """`exclude` is None or a contiguous (Q,) int32 tensor; returns it by name for the device check."""
     if exclude is None:
         return {}
-    if not isinstance(exclude, torch.Tensor):
-        raise RuntimeError("nearest: exclude is not a tensor")
-    if exclude.dtype != torch.int32 or exclude.dim() != 1 or not exclude.is_contiguous():
-        raise RuntimeError(f"nearest: exclude: expected a contiguous 1-D int32 tensor, got {exclude.dtype} of "
-                           f"shape {tuple(exclude.shape)}")
-    if exclude.numel() != Q:
-        raise RuntimeError(f"nearest: exclude has {exclude.numel()} entries, queries has {Q} rows")
+    _need.per_row(exclude, "exclude", torch.int32, Q, "queries has {} rows", expected="a contiguous 1-D int32 tensor",
+                  hint=False)
     return {"exclude": exclude}
 
 
 def _need_r2(r2, Q: int) -> dict:
     """`r2` is a number or a contiguous (Q,) float32 tensor; returns the tensor by name for the device check."""
-    if isinstance(r2, torch.Tensor):
-        if r2.dtype != torch.float32 or r2.dim() != 1 or not r2.is_contiguous():
-            raise RuntimeError(f"nearest: r2: expected a number or a contiguous 1-D float32 tensor, got {r2.dtype} of "
-                               f"shape {tuple(r2.shape)}")
-        if r2.numel() != Q:
-            raise RuntimeError(f"nearest: r2 has {r2.numel()} entries, queries has {Q} rows")
-        return {"r2": r2}
-    if isinstance(r2, bool) or not isinstance(r2, numbers.Real):
-        raise RuntimeError(f"nearest: r2 must be a number or a tensor, got {type(r2).__name__}")
-    return {}
+    per_query = _need.number_or_rows(r2, "r2", Q, "queries has {} rows",
+                                     expected="a number or a contiguous 1-D float32 tensor", hint=False)
+    return {"r2": r2} if per_query else {}
 
 
-def _need_out(out, want, Q: int) -> dict:
+def _need_out(out, want, n: int, of: str = "queries has {} rows", may_be_none: str = None) -> dict:
     """`out` is None or one tensor per entry of `want`, the expected (name, dtype, shape); a shape of None accepts
-    any contiguous 1-D tensor of Q entries.  Returns them by name for the device check."""
+    any contiguous 1-D tensor of n entries, `of` saying whose n it is.  The tensor named may_be_none may be left
+    out as None.  Returns them by name for the device check."""
     if out is None:
         return {}
     if not isinstance(out, (tuple, list)) or len(out) != len(want):
         raise RuntimeError(f"nearest: out must be a {'pair' if len(want) == 2 else 'triple'} "
                            f"({', '.join(what[len('out '):] for what, _, _ in want)})")
+    named = {}
     for t, (what, dtype, shape) in zip(out, want):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"nearest: {what} is not a tensor")
+        if t is None and what == may_be_none:
+            continue
         if shape is None:
-            if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
-                raise RuntimeError(f"nearest: {what}: expected a contiguous 1-D {dtype} tensor, got {t.dtype} of "
-                                   f"shape {tuple(t.shape)}")
-            if t.numel() != Q:
-                raise RuntimeError(f"nearest: {what} has {t.numel()} entries, queries has {Q} rows")
-        elif t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RuntimeError(f"nearest: {what}: expected a contiguous {shape} {dtype} tensor, got "
-                               f"{t.dtype} of shape {tuple(t.shape)}")
-    return {what: t for t, (what, _, _) in zip(out, want)}
+            _need.per_row(t, what, dtype, n, of, hint=False)
+        else:
+            _need.tensor(t, what, dtype, shape, lambda t: tuple(t.shape) == shape, hint=False)
+        named[what] = t
+    return named
 
 
 class NearestIndex:
@@ -131,7 +96,7 @@ class NearestIndex:
         self.P = _need_rows(points, "points")
         if self.P:
             _lib.device_of(points)
-        _need_gpu(None, points=points)
+        _need.gpu(None, points=points)
         self.device = points.device
         self._scratch = {}
         L = _lib.lib()
@@ -147,7 +112,7 @@ class NearestIndex:
     def _need_device(self, Q: int, **tensors) -> None:
         if Q:
             _lib.device_of(*tensors.values())
-        _need_gpu(self.device, **tensors)
+        _need.gpu(self.device, **tensors)
 
     def _scratch_for(self, stream, Q: int, need_bytes):
         """The scratch tensor of `stream` and Q's size class, of need_bytes(that class's Q) bytes at least; None for
@@ -225,22 +190,9 @@ class NearestIndex:
         reuses three such tensors.  Runs on the current stream; no host synchronisation."""
         Q = _need_rows(queries, "queries")
         k = _need_k(k, 0)
-        if max_count is None:
-            max_count = _MAX
-        if isinstance(max_count, bool) or not isinstance(max_count, numbers.Integral):
-            raise RuntimeError(f"nearest: max_count must be an integer or None, got {type(max_count).__name__}")
-        max_count = int(max_count)
-        if not max(k, 1) <= max_count <= _MAX:
-            raise RuntimeError(f"nearest: max_count must be in [max(k, 1), 2^31 - 1], got {max_count} with k = {k}")
-        if isinstance(r2, torch.Tensor):
-            if r2.dtype != torch.float32 or r2.dim() != 1 or not r2.is_contiguous():
-                raise RuntimeError(f"nearest: r2: expected a number or a contiguous 1-D float32 tensor, got {r2.dtype} of "
-                                   f"shape {tuple(r2.shape)}")
-            if r2.numel() != Q:
-                raise RuntimeError(f"nearest: r2 has {r2.numel()} entries, queries has {Q} rows")
-        elif isinstance(r2, bool) or not isinstance(r2, numbers.Real):
-            raise RuntimeError(f"nearest: r2 must be a number or a tensor, got {type(r2).__name__}")
-        tensors = {"queries": queries, **({"r2": r2} if isinstance(r2, torch.Tensor) else {}), **_need_exclude(exclude, Q),
+        max_count = _need.integer(_wrap.MAX if max_count is None else max_count, "max_count", max(k, 1), _wrap.MAX,
+                                  "an integer or None", span="[max(k, 1), 2^31 - 1]", tail=f" with k = {k}")
+        tensors = {"queries": queries, **_need_r2(r2, Q), **_need_exclude(exclude, Q),
                    **_need_out(out, (("out count", torch.int32, (Q,)), ("out idx", torch.int32, (Q, k)),
                                      ("out d2", torch.float32, (Q, k))), Q)}
         self._need_device(Q, **tensors)
@@ -296,33 +248,15 @@ class NearestIndex:
         is the number of entries all lists hold.  Runs on the current stream."""
         Q = _need_rows(queries, "queries")
         if capacity is not None:
-            if isinstance(capacity, bool) or not isinstance(capacity, numbers.Integral):
-                raise RuntimeError(f"nearest: capacity must be an integer or None, got {type(capacity).__name__}")
-            capacity = int(capacity)
-            if not 0 <= capacity <= _MAX:
-                raise RuntimeError(f"nearest: capacity must be in [0, 2^31 - 1], got {capacity}")
-        if not isinstance(distances, bool):
-            raise RuntimeError(f"nearest: distances must be a bool, got {type(distances).__name__}")
+            capacity = _need.integer(capacity, "capacity", 0, _wrap.MAX, "an integer or None", span="[0, 2^31 - 1]")
+        _need.flag(distances, "distances")
         r2t = _need_r2(r2, Q)
-        outs = {}
-        if out is not None:
-            if capacity is None:
-                raise RuntimeError("nearest: out=(rows, d2) needs a capacity")
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise RuntimeError("nearest: out must be a pair (rows, d2)")
-            for t, what, dtype in ((out[0], "out rows", torch.int32), (out[1], "out d2", torch.float32)):
-                if t is None and what == "out d2" and not distances:
-                    continue
-                if not isinstance(t, torch.Tensor):
-                    raise RuntimeError(f"nearest: {what} is not a tensor")
-                if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
-                    raise RuntimeError(f"nearest: {what}: expected a contiguous 1-D {dtype} tensor, got {t.dtype} of "
-                                       f"shape {tuple(t.shape)}")
-                if t.numel() != capacity:
-                    raise RuntimeError(f"nearest: {what} has {t.numel()} entries, capacity is {capacity}")
-                outs[what] = t
-            if not distances and out[1] is not None:
-                raise RuntimeError("nearest: out d2 must be None without distances")
+        if out is not None and capacity is None:
+            raise RuntimeError("nearest: out=(rows, d2) needs a capacity")
+        outs = _need_out(out, (("out rows", torch.int32, None), ("out d2", torch.float32, None)), capacity, "capacity is {}",
+                         may_be_none=None if distances else "out d2")
+        if "out d2" in outs and not distances:
+            raise RuntimeError("nearest: out d2 must be None without distances")
         tensors = {"queries": queries, **r2t, **_need_exclude(exclude, Q), **outs}
         self._need_device(Q, **tensors)
         with torch.cuda.device(self.device):
@@ -339,7 +273,7 @@ class NearestIndex:
             if capacity is None:
                 lo, hi = (int(v) & 0xFFFFFFFF for v in info[:2].tolist())  # the one host read
                 capacity = (hi << 32) | lo
-                if capacity > _MAX:
+                if capacity > _wrap.MAX:
                     raise RuntimeError(f"nearest: the lists hold {capacity} entries, more than 2^31 - 1: use a smaller radius "
                                        f"or fewer queries per call")
             rows, d2 = out if out is not None else (torch.empty(capacity, dtype=torch.int32, device=self.device),

@@ -23,32 +23,14 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _wrap
 
-_MAX = (1 << 31) - 1
 OPS = {"sum": 0, "mean": 1, "min": 2, "max": 3, "first": 4}  # HIDEGS_VOXEL_*
-
-
-def _need_tensor(t, what: str, dtype, shape_text: str, ok) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"voxel: {what} is not a tensor")
-    if t.dtype != dtype or not ok(t) or not t.is_contiguous():
-        raise RuntimeError(f"voxel: {what}: expected a contiguous {shape_text} {dtype} tensor, got {t.dtype} of shape "
-                           f"{tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'}")
-
-
-def _need_gpu(dev, **tensors) -> None:
-    for what, t in tensors.items():
-        if t.device.type != "cuda":
-            raise RuntimeError(f"voxel: {what}: expected a GPU tensor, got one on {t.device}")
-        if dev is not None and t.device != dev:
-            raise RuntimeError(f"voxel: tensors on different devices: the grid on {dev}, {what} on {t.device}")
+_need = _wrap.Checks("voxel", "the grid")
 
 
 def _need_count(n, what: str) -> int:
-    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
-        raise RuntimeError(f"voxel: {what} must be a non-negative int or None, got {n!r}")
-    return int(n)
+    return _need.integer(n, what, 0, math.inf, "a non-negative int or None")
 
 
 class VoxelGrid:
@@ -66,10 +48,7 @@ class VoxelGrid:
     """
 
     def __init__(self, points: torch.Tensor, cell: float, origin: torch.Tensor = None, among: torch.Tensor = None):
-        _need_tensor(points, "points", torch.float32, "(P, 3)", lambda t: t.dim() == 2 and t.shape[1] == 3)
-        P = self.P = points.shape[0]
-        if P > _MAX:
-            raise RuntimeError("voxel: points: at most 2^31 - 1 rows")
+        P = self.P = _need.cloud(points, "points")
         if isinstance(cell, bool) or not isinstance(cell, numbers.Real):
             raise RuntimeError(f"voxel: cell must be a number, got {type(cell).__name__}")
         cell = float(cell)
@@ -80,7 +59,7 @@ class VoxelGrid:
             raise RuntimeError(f"voxel: cell must be finite and > 0 as float32, with a finite 1 / cell, got {cell}")
         tensors = {"points": points}
         if origin is not None:
-            _need_tensor(origin, "origin", torch.float32, "(3,)", lambda t: tuple(t.shape) == (3,))
+            _need.tensor(origin, "origin", torch.float32, "(3,)", lambda t: tuple(t.shape) == (3,))
             tensors["origin"] = origin
         if among is not None:
             if not isinstance(among, torch.Tensor):
@@ -91,9 +70,8 @@ class VoxelGrid:
             if among.numel() != P:
                 raise RuntimeError(f"voxel: among has {among.numel()} entries, points has {P} rows")
             tensors["among"] = among
-        _need_gpu(None, points=points)
-        self.device = points.device
-        _need_gpu(self.device, **tensors)
+        self.device = _need.gpu(None, points=points)
+        _need.gpu(self.device, **tensors)
         self.cell = cell
         self._scratch = {}
         self._num_groups = None
@@ -146,20 +124,18 @@ class VoxelGrid:
         widths = []
         for i, t in enumerate(tensors):
             what = f"tensors[{i}]"
-            _need_tensor(t, what, torch.float32, "(P, ...)", lambda t: t.dim() >= 1)
+            _need.tensor(t, what, torch.float32, "(P, ...)", lambda t: t.dim() >= 1)
             if t.shape[0] != P:
                 raise RuntimeError(f"voxel: {what} has {t.shape[0]} rows, the grid has {P}")
             w = 1
             for d in t.shape[1:]:
                 w *= d
-            if w < 1 or w > _MAX:
+            if w < 1 or w > _wrap.MAX:
                 raise RuntimeError(f"voxel: {what}: rows of {w} values")
             widths.append(w)
             named[what] = t
         if weights is not None:
-            _need_tensor(weights, "weights", torch.float32, "(P,)", lambda t: t.dim() == 1)
-            if weights.numel() != P:
-                raise RuntimeError(f"voxel: weights has {weights.numel()} entries, the grid has {P} rows")
+            _need.per_row(weights, "weights", torch.float32, P, "the grid has {} rows", "(P,)")
             named["weights"] = weights
         if groups is not None:
             groups = _need_count(groups, "groups")
@@ -167,10 +143,10 @@ class VoxelGrid:
             if not isinstance(out, (list, tuple)) or len(out) != len(tensors):
                 raise RuntimeError(f"voxel: out must be a list of {len(tensors)} tensors")
             for i, t in enumerate(out):
-                _need_tensor(t, f"out[{i}]", torch.float32, "(groups, w)",
+                _need.tensor(t, f"out[{i}]", torch.float32, "(groups, w)",
                              lambda t, w=widths[i]: t.dim() == 2 and t.shape[1] == w)
                 named[f"out[{i}]"] = t
-        _need_gpu(self.device, **named)
+        _need.gpu(self.device, **named)
         n = self.num_groups if groups is None else groups
         if out is not None:
             for i, t in enumerate(out):

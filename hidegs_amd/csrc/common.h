@@ -204,6 +204,26 @@ __device__ __forceinline__ uint32_t wave_append(bool flag, uint32_t* counter)
     return base + (uint32_t)__popcll(m & lanes_below(lane));
 }
 
+// A global store with a cache policy, for output that is streamed out and not read again by its kernel
+// (its counterpart on the load side is __builtin_nontemporal_load):
+//   kPlain    an ordinary write-back store;
+//   kStream   global_store_* ... nt: the line is marked for early eviction from the L2;
+//   kThrough  global_store_dword/dwordx2 ... sc1: written through the L2 at agent scope.  4- and 8-byte
+//             values only; other sizes take the stream policy.
+// T is a scalar or a native ext_vector_type (for 16 bytes 4 x uint32_t: the builtin does not take uint4).
+enum StorePolicy { kPlain = 0, kStream = 1, kThrough = 2 };
+template <StorePolicy P, typename T>
+__device__ __forceinline__ void stream_store(T* p, const T v)
+{
+    if constexpr (P == kPlain) {
+        *p = v;
+    } else if constexpr (P == kThrough && (sizeof(T) == 4 || sizeof(T) == 8)) {
+        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        __builtin_nontemporal_store(v, p);
+    }
+}
+
 __device__ __forceinline__ bool finite3(float x, float y, float z)
 {
     return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;  // false for a NaN

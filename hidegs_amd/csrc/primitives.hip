@@ -307,7 +307,10 @@ int sort_pairs(void* scratch, size_t scratch_bytes, const K* keys_in, K* keys_ou
     }
     if (segmented) {
         uint64_t* ko = reinterpret_cast<uint64_t*>(keys_out);
-        if (packed)
+        if (packed && n <= kThroughMaxN)
+            HIDEGS_LAUNCH("segment_sort", (segment_sort_kernel<true, kThrough>), dim3(nseg + kScouts), dim3(kBlock), 0,
+                          stream, ko, vals_out, seg_starts, ranges_out, nseg, q);
+        else if (packed)
             HIDEGS_LAUNCH("segment_sort", segment_sort_kernel<true>, dim3(nseg + kScouts), dim3(kBlock), 0, stream, ko,
                           vals_out, seg_starts, ranges_out, nseg, q);
         else

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void radix_hist_kernel(const K* __restrict_
                                                             uint4* __restrict__ zero_jobs, uint32_t zero_count)
 {
     for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < zero_count; j += gridDim.x * kBlock)
-        zero_jobs[j] = make_uint4(0u, 0u, 0u, 0u);
+        zero_jobs[j] = make_uint4(0u, 0u, 0u, 0u);  // (as a kStream stream_store: level, profiles/r13_store_policy.md)
     __shared__ uint32_t s_hist[kWavesPerBlock][kRadix];
     const int t = threadIdx.x;
     const int wave = t / kWave;
@@ -155,7 +155,10 @@ __global__ __launch_bounds__(kBlock) void radix_hist_kernel(const K* __restrict_
         }
     }
     __syncthreads();
-    for (int d = t; d < kRadix; d += kBlock) {
+    // only the digit rows the pass has: radix_digit_scan_kernel's grid is mask + 1 rows, and radix_scatter_kernel
+    // loads the rows above `mask` only into digits that no item has (a 6-bit pass wrote 192 rows of scattered
+    // 4-byte stores that nothing read: 12.3 -> 11.1 us per launch at the 1080p view)
+    for (int d = t; d <= (int)mask; d += kBlock) {
         uint32_t c = 0;
 #pragma unroll
         for (int w = 0; w < kWavesPerBlock; w++) c += s_hist[w][d];
@@ -427,6 +430,9 @@ __global__ __launch_bounds__(kSBlock) __attribute__((amdgpu_waves_per_eu(D == kR
             const int i = t + j * kSBlock;
             if (i < count) {
                 const uint32_t d = s_off[s_digit[i]] + i;
+                // (A plain store: stream_store's kThrough here measured +3.7 us per step and kStream +15 us, and
+                // +5 / +13 us when only the 128-byte lines wholly inside a digit run took the policy; the digit
+                // bytes below as kStream +4 us: profiles/r13_store_policy.md.)
                 if (d < n) keys_out[d] = s_stage[i];  // always true for consistent counts
             }
         }

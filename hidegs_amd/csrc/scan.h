@@ -83,6 +83,7 @@ __global__ __launch_bounds__(kBlock) void scan_downsweep_kernel(const uint32_t* 
     if (base + kDevScanTile <= n && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
         uint4* dst = reinterpret_cast<uint4*>(out + base);
 #pragma unroll
+        // (as kStream stream_stores: level, 149.3-149.8 against 149.2-150.8 us per step, profiles/r13_store_policy.md)
         for (int j = 0; j < kDevScanItems / 4; j++) dst[j * kBlock + threadIdx.x] = reinterpret_cast<uint4*>(s_tile)[j * kBlock + threadIdx.x];
     } else {
 #pragma unroll

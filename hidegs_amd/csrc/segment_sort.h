@@ -71,6 +71,7 @@ __device__ __forceinline__ void seg_load(const uint64_t* __restrict__ src_k, con
 }
 
 // The pairs seg_load<true> expanded, written back where they were read (each thread its own elements).
+template <StorePolicy P = kPlain>
 __device__ __forceinline__ void store_loaded(const uint64_t (&k)[kSegItems], const uint32_t (&v)[kSegItems],
                                              const uint32_t begin, const uint32_t m, uint64_t* dk, uint32_t* dv)
 {
@@ -78,8 +79,8 @@ __device__ __forceinline__ void store_loaded(const uint64_t (&k)[kSegItems], con
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = threadIdx.x + q * kBlock;
         if (i < m) {
-            dk[begin + i] = k[q];
-            dv[begin + i] = v[q];
+            stream_store<P>(&dk[begin + i], k[q]);
+            stream_store<P>(&dv[begin + i], v[q]);
         }
     }
 }
@@ -140,6 +141,7 @@ __device__ __forceinline__ uint32_t bucket_starts(const uint64_t (&k)[kSegItems]
 // Compact form, one high half (ref_hi) for the whole segment: {low half, value} records, 8 B per pair in
 // one LDS write at its final position and one read, so a segment of up to kSegCap pairs goes through LDS
 // in one pass; the keys are rebuilt on store.
+template <StorePolicy P = kPlain>
 __device__ __forceinline__ void stage_compact(const uint64_t (&k)[kSegItems], const uint32_t (&v)[kSegItems],
                                               const uint32_t (&pos)[kSegItems], const uint32_t begin,
                                               const uint32_t m, const uint32_t ref_hi, BucketShared& sh, uint64_t* dk,
@@ -157,13 +159,14 @@ __device__ __forceinline__ void stage_compact(const uint64_t (&k)[kSegItems], co
         const uint32_t i = t + q * kBlock;
         if (i < m) {
             const uint2 rec = stage[i];
-            dk[begin + i] = khi | rec.x;
-            dv[begin + i] = rec.y;
+            stream_store<P>(&dk[begin + i], khi | rec.x);
+            stream_store<P>(&dv[begin + i], rec.y);
         }
     }
 }
 
 // Whole keys: keys and values together for up to kSegRun pairs, else the keys, then the values.
+template <StorePolicy P = kPlain>
 __device__ __forceinline__ void stage_pairs(const uint64_t (&k)[kSegItems], const uint32_t (&v)[kSegItems],
                                             const uint32_t (&pos)[kSegItems], const uint32_t begin, const uint32_t m,
                                             BucketShared& sh, uint64_t* dk, uint32_t* dv)
@@ -184,8 +187,8 @@ __device__ __forceinline__ void stage_pairs(const uint64_t (&k)[kSegItems], cons
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = t + q * kBlock;
         if (i < m) {
-            dk[begin + i] = stage_k[i];
-            if (together) dv[begin + i] = stage_v[i];
+            stream_store<P>(&dk[begin + i], stage_k[i]);
+            if (together) stream_store<P>(&dv[begin + i], stage_v[i]);
         }
     }
     if (together) return;
@@ -198,7 +201,7 @@ __device__ __forceinline__ void stage_pairs(const uint64_t (&k)[kSegItems], cons
 #pragma unroll
     for (int q = 0; q < kSegItems; q++) {
         const uint32_t i = t + q * kBlock;
-        if (i < m) dv[begin + i] = stage_v[i];
+        if (i < m) stream_store<P>(&dv[begin + i], stage_v[i]);
     }
 }
 
@@ -355,6 +358,7 @@ __device__ __forceinline__ void open_local(const uint64_t* keys, const BigQueue&
 // kExpandItems loads in flight.  The low halves keep their values and places, so whoever reads only
 // those meanwhile (a scout's open_local) sees no change.
 constexpr int kExpandItems = 8;
+template <StorePolicy P = kPlain>
 __device__ __forceinline__ void expand_records(uint64_t* keys, uint32_t* vals, const uint32_t begin, const uint32_t m,
                                                const uint32_t seg)
 {
@@ -371,8 +375,8 @@ __device__ __forceinline__ void expand_records(uint64_t* keys, uint32_t* vals, c
         for (int u = 0; u < kExpandItems; u++) {
             const uint32_t i = i0 + u * kBlock + threadIdx.x;
             if (i < m) {
-                keys[begin + i] = khi | rec[u].x;
-                vals[begin + i] = rec[u].y;
+                stream_store<P>(&keys[begin + i], khi | rec[u].x);
+                stream_store<P>(&vals[begin + i], rec[u].y);
             }
         }
     }
@@ -383,7 +387,16 @@ __device__ __forceinline__ void expand_records(uint64_t* keys, uint32_t* vals, c
 // Packed: `keys` arrives as packed records and segment b's high key half is b.  Every way out leaves
 // whole keys and values behind; a segment that this kernel does not sort itself is expanded in place
 // by its own workgroup first, so the queue's kernels and the one-workgroup forms see ordinary pairs.
-template <bool Packed>
+// Out: the policy of the stores that leave a sorted (or expanded) segment behind for the caller -- stage_compact,
+// stage_pairs, expand_records, store_loaded.  They are contiguous runs that this kernel does not read again (but for
+// store_loaded's, which the same workgroup's LSD form reads behind a barrier); written
+// through (kThrough), a workgroup's lines leave the L2 while the others still sort instead of all at the kernel's end:
+// segment_sort 40.4 -> 38.6 us at the 1080p view, the step -1.9 us.  Only up to kThroughMaxN pairs: the 4K frame's
+// 42.9M pairs, whose output no longer fits the 256 MB MALL, went 0.699 -> 0.719 ms per step (kStream: +0.5 us at
+// 1080p; profiles/r13_store_policy.md).  ranges_out, the queue's hand-offs (a hot tile's expansion, emit_jobs,
+// record_run, the pool) and sort_segment, which piece_sort_kernel shares, keep plain stores.
+constexpr long long kThroughMaxN = kNarrowMaxN;
+template <bool Packed, StorePolicy Out = kPlain>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Packed ? kSegWavesPacked : kSegWaves)))
 void segment_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, const uint32_t* __restrict__ starts,
                          uint2* __restrict__ ranges_out, const int nseg, const BigQueue q)
@@ -447,7 +460,7 @@ void segment_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ val
     if (ranges_out && threadIdx.x == 0) ranges_out[seg] = r.y > r.x ? r : make_uint2(0u, 0u);
     const uint32_t begin = r.x, m = r.y - r.x;
     if (r.y <= r.x + 1) {  // absent or single pair: already in place
-        if (Packed && r.y == r.x + 1) expand_records(keys, vals, begin, 1u, seg);
+        if (Packed && r.y == r.x + 1) expand_records<Out>(keys, vals, begin, 1u, seg);
         return;
     }
     if (m > (uint32_t)kSegCap) {
@@ -491,7 +504,7 @@ void segment_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ val
     const SegRange st = segment_range(lo, hi, s_and, s_or);
     if (st.lo == st.hi) {  // equal low keys: the input order is the stable order
         // (read again, not stored from k and v: keeping those live to here costs scratch)
-        if (Packed) expand_records(keys, vals, begin, m, seg);
+        if (Packed) expand_records<Out>(keys, vals, begin, m, seg);
         return;
     }
     const int shift = st.shift;
@@ -499,7 +512,7 @@ void segment_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ val
     const uint32_t fullest = bucket_starts<Packed>(k, m, st.lo, shift, hd, sh, s_and, s_max, mixed_hi);
     if (fullest > (uint32_t)kMaxBucket || shift + kIndexBits > 32) {  // crowded depths, or fields too
         // wide for 32 bits: the LSD form (block-uniform branch), which reads whole pairs
-        if (Packed) store_loaded(k, v, begin, m, keys, vals);
+        if (Packed) store_loaded<Out>(k, v, begin, m, keys, vals);
         // the bits that vary, from the registers; its barrier also publishes the pairs just stored
         // (s_and is still being read; s_max and s_or are free)
         const uint32_t diff = segment_diff(k, m, s_max, s_or);
@@ -539,10 +552,10 @@ void segment_sort_kernel(uint64_t* __restrict__ keys, uint32_t* __restrict__ val
     }
     __syncthreads();
     if (Packed || !mixed_hi) {  // (Packed: one high half by construction)
-        stage_compact(k, v, pos, begin, m, ref_hi, sh, keys, vals);
+        stage_compact<Out>(k, v, pos, begin, m, ref_hi, sh, keys, vals);
         return;
     }
-    stage_pairs(k, v, pos, begin, m, sh, keys, vals);
+    stage_pairs<Out>(k, v, pos, begin, m, sh, keys, vals);
 }
 
 // The last workgroup to count `pending` down (a record's phase, or a chunk group of its HIST phase)

@@ -24,6 +24,7 @@
 
 #include "../../include/hidegs_moments.h"
 #include "common.h"
+#include "neighbor_sum.h"  // kSum: the positions of a block of the rule
 
 namespace hidegs {
 namespace {
@@ -31,7 +32,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;  // 4
 constexpr long long kMomentsMax = 0x7fffffffLL;
-constexpr uint32_t kSum = 64;        // positions of a block of the rule
 constexpr uint32_t kLaneBlocks = 4;  // blocks of the longest list that one lane sums
 constexpr int kLaneGridCap = 8192;   // workgroups of moments_short, moments_lane and sym3_eigen: 32 per CU, then by stride
 constexpr int kWaveGrid = 2048;      // workgroups of moments_wave: 8 per CU

@@ -1,8 +1,8 @@
 """ctypes binding of the C ABI in include/hidegs.h, include/hidegs_rows.h, include/hidegs_resize.h,
 include/hidegs_clone.h, include/hidegs_topk.h, include/hidegs_nearest.h, include/hidegs_nearest_k.h,
 include/hidegs_nearest_within.h, include/hidegs_nearest_lists.h, include/hidegs_voxel.h,
-include/hidegs_moments.h, include/hidegs_components.h and include/hidegs_neighbor_reduce.h
-(hidegs_amd/libhidegs.so).
+include/hidegs_moments.h, include/hidegs_components.h, include/hidegs_neighbor_reduce.h and
+include/hidegs_neighbor_grad.h (hidegs_amd/libhidegs.so).
 
 This is the only place that loads the native library.  It fails loudly: a missing
 library raises ImportError-like RuntimeError at first use, and a non-zero return
@@ -206,6 +206,24 @@ FIELDS_SIGNATURES = {
     "hidegs_neighbor_reduce_lists": (I, [P, SZ, P, I, LL, P, P, P, P, LL, LL, P, P]),
 }
 
+
+
+class NeighborGradField(C.Structure):
+    """hidegs_neighbor_grad_field (include/hidegs_neighbor_grad.h)."""
+    _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("grad_out", C.c_void_p), ("grad_src", C.c_void_p),
+                ("width", C.c_int), ("op", C.c_int)]
+
+
+# include/hidegs_neighbor_grad.h, in its order
+FIELDS_GRAD_SIGNATURES = {
+    "hidegs_neighbor_transpose_scratch_bytes": (SZ, [LL]),
+    "hidegs_neighbor_transpose_table": (I, [P, SZ, LL, P, LL, I, P, P, P, P, P]),
+    "hidegs_neighbor_transpose_lists": (I, [P, SZ, LL, P, P, LL, LL, P, P, P, P, P]),
+    "hidegs_neighbor_reduce_backward_scratch_bytes": (SZ, [LL, LL]),
+    "hidegs_neighbor_reduce_backward_table": (I, [P, SZ, P, I, LL, P, P, P, LL, I, P, P, P, P, P, P, P]),
+    "hidegs_neighbor_reduce_backward_lists": (I, [P, SZ, P, I, LL, P, P, P, P, LL, LL, P, P, P, P, P, P, P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -213,7 +231,7 @@ _lock = threading.Lock()
 def load_library(path: str) -> C.CDLL:
     """A build of the ABI at `path` with every signature of include/hidegs.h, hidegs_rows.h, hidegs_resize.h,
     hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h, hidegs_nearest_within.h, hidegs_nearest_lists.h,
-    hidegs_voxel.h, hidegs_moments.h, hidegs_components.h and hidegs_neighbor_reduce.h bound (lib() for the product build;
+    hidegs_voxel.h, hidegs_moments.h, hidegs_components.h, hidegs_neighbor_reduce.h and hidegs_neighbor_grad.h bound (lib() for the product build;
     tests load the build.VARIANTS this way)."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m hidegs_amd.build` "
@@ -222,7 +240,8 @@ def load_library(path: str) -> C.CDLL:
     for name, (res, args) in {**SIGNATURES, **ROW_SIGNATURES, **RESIZE_SIGNATURES, **CLONE_SIGNATURES,
                               **TOPK_SIGNATURES, **NEAREST_SIGNATURES, **NEAREST_K_SIGNATURES,
                               **NEAREST_WITHIN_SIGNATURES, **NEAREST_LISTS_SIGNATURES, **VOXEL_SIGNATURES,
-                              **MOMENTS_SIGNATURES, **COMPONENTS_SIGNATURES, **FIELDS_SIGNATURES}.items():
+                              **MOMENTS_SIGNATURES, **COMPONENTS_SIGNATURES, **FIELDS_SIGNATURES,
+                              **FIELDS_GRAD_SIGNATURES}.items():
         fn = getattr(dll, name)
         fn.restype = res
         fn.argtypes = args

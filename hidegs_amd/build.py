@@ -1,6 +1,6 @@
 """Build recipe for hidegs_amd/libhidegs.so (the C-ABI library of include/hidegs.h, hidegs_rows.h,
 hidegs_resize.h, hidegs_clone.h, hidegs_topk.h, hidegs_nearest.h, hidegs_nearest_k.h, hidegs_nearest_within.h,
-hidegs_nearest_lists.h, hidegs_voxel.h, hidegs_moments.h, hidegs_components.h and hidegs_neighbor_reduce.h).
+hidegs_nearest_lists.h, hidegs_voxel.h, hidegs_moments.h, hidegs_components.h, hidegs_neighbor_reduce.h and hidegs_neighbor_grad.h).
 
 Built in-tree with hipcc for gfx950 so the .so travels to the GPU box with the
 repository snapshot.  `python -m hidegs_amd.build` or `__graft_entry__.build()`.
@@ -29,7 +29,7 @@ OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhidegs.so")
 VARIANT_DIR = os.path.join(HERE, "variants")
 SOURCES = ["abi.cpp", "timing.cpp", "primitives.hip", "knn.hip", "adam.hip", "wire.hip", "rows.hip", "topk.hip",
-           "nearest.hip", "voxel.hip", "moments.hip", "components.hip", "neighbor_reduce.hip"]
+           "nearest.hip", "voxel.hip", "moments.hip", "components.hip", "neighbor_reduce.hip", "neighbor_grad.hip"]
 # every header: a change to any of them rebuilds every object
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "hidegs.h"),
                                                          os.path.join(INCLUDE, "hidegs_rows.h"),
@@ -43,7 +43,8 @@ HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, 
                                                          os.path.join(INCLUDE, "hidegs_voxel.h"),
                                                          os.path.join(INCLUDE, "hidegs_moments.h"),
                                                          os.path.join(INCLUDE, "hidegs_components.h"),
-                                                         os.path.join(INCLUDE, "hidegs_neighbor_reduce.h")]
+                                                         os.path.join(INCLUDE, "hidegs_neighbor_reduce.h"),
+                                                         os.path.join(INCLUDE, "hidegs_neighbor_grad.h")]
 
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf, so the
 # oracle (oracle/knn_ref.c) can reproduce each rounding step bit for bit.

@@ -58,6 +58,10 @@ uint32_t take_async_bits(hipStream_t stream);
 size_t sort_u64_scratch(long long n);
 int sort_pairs_u64(void* scratch, size_t bytes, const uint64_t* ki, uint64_t* ko, const uint32_t* vi, uint32_t* vo,
                    long long n, int b, int e, hipStream_t s);
+// The same over u32 keys, as the neighbour-list transpose (neighbor_grad.hip) calls it.
+size_t sort_u32_scratch(long long n);
+int sort_pairs_u32(void* scratch, size_t bytes, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo,
+                   long long n, int b, int e, hipStream_t s);
 
 // 256-byte aligned carving of one caller-provided scratch buffer.
 constexpr size_t kAlign = 256;
